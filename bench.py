@@ -11,9 +11,18 @@ time is the max over ranks.  value = packet events (executed deliver-packet
 events, worker.c:253) of all ranks / time.
 
 Also reported: the APSP path-cache build time for the same 10k-vertex topology
-(BASELINE metric 2), a roofline object for the round kernel (HIP-event device
-time on the engine's stream; algorithmic bytes defined in DESIGN.md), and the
-oracle's serial CPU loop as cpu_baseline (rank 0, N = 1 only).
+(BASELINE metric 2) and a roofline object for the round kernel (HIP-event
+device time on the engine's stream over the timed steps; algorithmic bytes
+defined in DESIGN.md).
+
+A plain run does only that: set-up, warm-up, the K timed steps, the result
+line.  --full adds the legs that take runs of their own: the oracle's serial
+CPU loop and the reference's own loop as cpu_baseline (rank 0, N = 1 only), the
+lossy C3 run and, at N > 1, the parity check against one engine; without it
+their keys are null.  --dump-outputs DIR
+writes what the timed path left after its last step (every host's end state,
+the timed call's counts) as DIR/<name>.npy in float64; the inputs are seeded,
+so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -80,8 +89,11 @@ def parse():
                     help="skip timing the reference's own serial loop (oracle/_ref/libshdref_loop.so)")
     ap.add_argument("--reference-window-ms", type=int, nargs=2, default=[1100, 1200],
                     help="the simulated window [t0, t1) over which the reference's own loop is timed")
-    ap.add_argument("--cpu-sample-steps", type=int, default=0,
-                    help="timed steps the CPU baseline runs (0 = all of them: the same window as value)")
+    ap.add_argument("--cpu-sample-steps", type=int, default=8,
+                    help="the most warm-up steps and the most timed steps the CPU baseline runs, so that its cost "
+                         "does not grow with --steps / --warmup (the headline's population is stationary, so the "
+                         "rate does not depend on the window; default 8: at the default --steps 8 --warmup 2 the "
+                         "same window as value); 0 = all of them")
     ap.add_argument("--exchange", choices=["p2p", "rccl", "torch"], default="p2p",
                     help="N > 1: p2p = shd_xgroup with the peer-to-peer transport (each rank's receive blocks "
                          "IPC-mapped by every rank and stored into over xGMI, tagged headers, in-kernel waits; "
@@ -94,7 +106,40 @@ def parse():
     ap.add_argument("--group", action="store_true",
                     help="run the shd_xgroup path even at N = 1 (a one-rank RCCL group)")
     ap.add_argument("--quiet", action="store_true")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline: cpu_baseline (with the reference's own loop), "
+                         "lossy_c3, parity at N > 1, the tcp workload's CPU sample; --no-cpu-baseline, "
+                         "--no-reference-cpu, --lossy-edge-loss-max 0 and --no-parity still drop one each")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they left as DIR/<name>.npy (float64, at most 64 MB "
+                         "in all): host_state (one row per host, shd_eng_digest's columns; a fixed seeded sample "
+                         "of the hosts when they exceed the limit) and run_stats; at N > 1 one host_state per rank")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(dirname, rank, world, host_state, run_stats):
+    """--dump-outputs: host_state (a structured per-host array, this rank's
+    hosts) as [hosts, fields] float64 and run_stats (name -> count, rank 0) as
+    a float64 vector in the order given.  float64 holds every counter and every
+    time in ns exactly (below 2^53).  Beyond the byte limit (shared by the
+    ranks) the hosts are a fixed seeded sample, the same from run to run."""
+    os.makedirs(dirname, exist_ok=True)
+    names = host_state.dtype.names
+    rows_max = (DUMP_BYTES_MAX // max(world, 1) - 4096) // (8 * len(names))
+    if len(host_state) > rows_max:
+        host_state = host_state[np.sort(np.random.default_rng(0).choice(len(host_state), rows_max, replace=False))]
+    table = np.stack([host_state[n].astype(np.float64) for n in names], axis=1)
+    np.save(os.path.join(dirname, "host_state.npy" if world <= 1 else "host_state_rank%d.npy" % rank), table)
+    if rank == 0:
+        np.save(os.path.join(dirname, "run_stats.npy"), np.array(list(run_stats.values()), dtype=np.float64))
+        log(rank, "dumped to %s: host_state %s (%s), run_stats (%s)"
+            % (dirname, table.shape, ", ".join(names), ", ".join(run_stats)))
 
 
 class Roctx:
@@ -371,17 +416,23 @@ def main():
                 "packet_events_per_launch": round(pkt_all / max(launches, 1), 1),
                 "active_hosts_per_launch": round(hr_all / max(launches, 1), 1)}
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, eng.digest(),
+                     {"n_events": evs, "n_pkt_events": pkt, "n_rounds": rounds,
+                      "final_time_ns": getattr(st, "final_time", end_time)})
+
+    # the legs beside the headline (--full): each takes runs of its own
     parity = None
-    if world > 1 and not args.no_parity:
+    if args.full and world > 1 and not args.no_parity:
         parity = parity_leg(args, S, g, att, model, eng, pb, rank, world, dev, end_time, dist, torch, tdev,
                             int(getattr(wst, "n_pkt_events", getattr(wst, "pkt_events", 0))) + int(pkt))
 
     lossy = None
-    if world == 1 and args.lossy_edge_loss_max > 0 and not use_group and args.workload == "c3":
+    if args.full and world == 1 and args.lossy_edge_loss_max > 0 and not use_group and args.workload == "c3":
         lossy = lossy_leg(args, S, W, Engine, PathCache, host_vertex, step, end_time, dev, torch)
 
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu_baseline = cpu_leg(args, S, W, g, model, step, value)
         if args.workload == "c3" and not args.no_reference_cpu:
             cpu_baseline["reference"] = reference_leg(args, S, W, g, host_vertex)
@@ -538,6 +589,14 @@ def tcp_main(args):
         dist.all_reduce(mx, op=dist.ReduceOp.MAX)
         events, deliv = int(red[0].item()), int(red[1].item())
         dev_s, wall = float(mx[0].item()), float(mx[1].item())
+    if args.dump_outputs:   # the last run's result, this rank's hosts
+        state = np.empty(len(r["next_event_id"]), dtype=[("next_event_id", "<u8"), ("next_packet_id", "<u8"),
+                                                         ("rng_probe", "<u4")])
+        for k in state.dtype.names:
+            state[k] = r[k]
+        dump_outputs(args.dump_outputs, rank, world, state,
+                     {"events": r["events"], "rounds": r["rounds"], "deliveries": r["deliveries"]})
+    if dist is not None:
         comm.close()
         if rank != 0:
             dist.destroy_process_group()
@@ -549,7 +608,7 @@ def tcp_main(args):
     per_round_us = r["device_ms"] * 1e3 / max(r["rounds"], 1)
     achieved = alg / (r["device_ms"] / 1e3) / 1e9
     cpu = None
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         # bounded sample: the same model at min(H, 4096) hosts (the same
         # per-pair work); the GPU runs that sample too, and the end states of
         # every host must agree
@@ -727,7 +786,8 @@ def cpu_leg(args, S, W, g, model, step, value):
         the result is the serial one; first touches resolved at each round's
         end in serial order) --
     and both end states compared bit for bit.  --cpu-sample-steps bounds the
-    window (default: all timed steps)."""
+    warm-up and the window (default: 8 steps each, so the leg's cost does not
+    grow with --steps; the window it ran is in `sample`)."""
     sys.path.insert(0, os.path.join(REPO, "tests"))
     try:
         import oracle_ffi as O
@@ -736,7 +796,8 @@ def cpu_leg(args, S, W, g, model, step, value):
         return {"value": None, "unit": "packet events/s", "cores": 1, "kind": "port",
                 "sample": f"oracle unavailable: {ex}"}
     n_steps = args.steps if args.cpu_sample_steps <= 0 else min(args.steps, args.cpu_sample_steps)
-    t_mark = args.warmup * step
+    w_steps = args.warmup if args.cpu_sample_steps <= 0 else min(args.warmup, args.cpu_sample_steps)
+    t_mark = w_steps * step
     t_end = t_mark + n_steps * step
     m = model
     host_vertex = model.host_vertex

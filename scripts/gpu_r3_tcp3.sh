@@ -9,7 +9,7 @@ timeout -k 10 300 python -u -m pytest tests/test_tcp_gpu.py -x -v --timeout 120 
 tail -2 $O/tcp_tests.log
 timeout -k 10 300 python3 bench.py --workload tcp --hosts-per-gpu 4096 --steps 1 --warmup 1 --no-cpu-baseline > $O/tcp_4096.json 2> $O/tcp_4096.err || { tail $O/tcp_4096.err; exit 2; }
 cat $O/tcp_4096.json
-timeout -k 10 600 python3 bench.py --workload tcp --steps 2 --warmup 1 > $O/tcp_bench.json 2> $O/tcp_bench.err || { tail $O/tcp_bench.err; exit 3; }
+timeout -k 10 600 python3 bench.py --full --workload tcp --steps 2 --warmup 1 > $O/tcp_bench.json 2> $O/tcp_bench.err || { tail $O/tcp_bench.err; exit 3; }
 cat $O/tcp_bench.json
 SHD_TCP_LANES=16 timeout -k 10 300 python3 bench.py --workload tcp --steps 1 --warmup 1 --no-cpu-baseline > $O/tcp_lanes16.json 2> $O/tcp_lanes16.err || { tail $O/tcp_lanes16.err; exit 4; }
 cat $O/tcp_lanes16.json

@@ -14,5 +14,5 @@ for rep in 1; do
   echo "rep $rep global-offsets: $(tail -1 $O/apsp_glb_$rep.log)"
   echo "rep $rep lds-offsets:    $(tail -1 $O/apsp_lds_$rep.log)"
 done
-timeout -k 10 900 python -u bench.py --workload tcp --steps 3 --warmup 1 > $O/tcp_bench.json 2> $O/tcp_bench.err
+timeout -k 10 900 python -u bench.py --full --workload tcp --steps 3 --warmup 1 > $O/tcp_bench.json 2> $O/tcp_bench.err
 echo "tcp bench rc=$?"; tail -3 $O/tcp_bench.err; cat $O/tcp_bench.json

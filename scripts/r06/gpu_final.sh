@@ -8,5 +8,5 @@ timeout -k 10 1100 python3 -u -m pytest tests -x -q -m gpu --timeout 600 --timeo
 tail -3 $O/tests.log
 [ $rc -eq 0 ] || exit 1
 timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1 || exit 2
-timeout -k 10 600 python3 bench.py > $O/bench.json 2> $O/bench.err || exit 3
+timeout -k 10 600 python3 bench.py --full > $O/bench.json 2> $O/bench.err || exit 3
 echo final done

@@ -1,6 +1,6 @@
 #!/bin/bash
 # profiles/r06 (C3 headline) from one GPU call; raw traces reduced on the box:
-#   bench.json              bench.py defaults (C3 headline, CPU baseline on the same window)
+#   bench.json              bench.py --full defaults (C3 headline, CPU baseline on the same window)
 #   timed_region.json       rocprofv3 --kernel-trace --marker-trace: round kernel time inside bench's timed region
 #   bench_kernel_stats.csv  the same run's --stats summary (whole run)
 #   pmc_calibration.json    FETCH_SIZE / WRITE_SIZE against known bytes (scripts/microbench/pmc_calib.hip)
@@ -12,7 +12,7 @@ export TMPDIR=/tmp
 O=gpurun_out/r06pa
 rm -rf $O; mkdir -p $O
 ARGS="--steps 4 --warmup 2 --no-cpu-baseline --lossy-edge-loss-max 0"
-timeout -k 10 600 python3 bench.py > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
+timeout -k 10 600 python3 bench.py --full > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
 echo bench ok
 timeout -k 10 400 rocprofv3 --kernel-trace --marker-trace --stats --output-format csv -d $O/tr -o run -- \
     python3 bench.py $ARGS > $O/bench_rocprof.json 2> $O/tr.err || { tail $O/tr.err; exit 2; }

@@ -12,7 +12,7 @@ export TMPDIR=/tmp
 O=gpurun_out/r02
 rm -rf $O; mkdir -p $O
 ARGS="--steps 2 --warmup 2 --no-cpu-baseline --lossy-edge-loss-max 0"
-timeout -k 10 400 python3 bench.py > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
+timeout -k 10 400 python3 bench.py --full > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o run -- \
     python3 bench.py $ARGS > $O/bench_under_rocprof.json 2> $O/trace.err || { tail $O/trace.err; exit 2; }
 cp "$(find $O/trace -name '*kernel_stats.csv' | head -1)" $O/bench_kernel_stats.csv && rm -rf $O/trace || exit 2

@@ -1,4 +1,4 @@
-"""bench.py at N > 1 checks its own end state (round 6): after the timed
+"""bench.py --full at N > 1 checks its own end state (round 6): after the timed
 region every rank hashes its hosts' end states and rank 0 runs the whole model
 on one engine of its own GPU over the same [0, end); the line carries
 "parity" and the transport that actually ran.  Rehearsed here with two ranks
@@ -33,7 +33,7 @@ def test_bench_rehearsal_checks_the_group_against_one_engine(drop):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(REPO, "bench.py"), "--gpus", "2", "--comm", "host", "--steps", "1", "--warmup", "1",
-           "--hosts-per-gpu", "2000", "--vertices", "2000", "--no-cpu-baseline"]
+           "--hosts-per-gpu", "2000", "--vertices", "2000", "--full", "--no-cpu-baseline"]
     p = subprocess.run(cmd, env=env, cwd=REPO, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert p.returncode == 0, p.stderr.decode(errors="replace")[-3000:]
     line = json.loads(p.stdout.decode().strip().splitlines()[-1])
