@@ -120,9 +120,13 @@ typedef struct shd_config_host {
     uint64_t bw_up_kibps;
     uint64_t heartbeat_s;   /* 0 = the option default */
     int32_t n_processes;    /* <process> / <application> children, document order */
-    int32_t _pad;
+    int32_t logpcap;        /* <host logpcap>: 1 when it is "true" in any letter case
+                             * (configuration.c:443-445, master.c:352), else 0 */
     uint64_t* process_start_s;   /* [n_processes] starttime (or legacy time), seconds
                                   * (configuration.c:576-579; master.c:299 scales by 1 s) */
+    char* pcapdir;          /* <host pcapdir> (configuration.c:446-448, master.c:353), NULL
+                             * when absent: the directory of the host's pcap files
+                             * (shdtcp.h shd_pcap_write_host) */
 } shd_config_host;
 typedef struct shd_config {
     int32_t n_hosts;

@@ -88,7 +88,41 @@ typedef struct shd_tcp_model {
     const double* dest_cum;
     const uint8_t* host_class;
     int32_t n_classes, _pad2;
+    /* Packet capture (the reference's <host logpcap="true">,
+     * network_interface.c:337-373): pcap_host[h] != 0 makes host h a capture
+     * host; NULL: none.  A capture host's lane writes one shd_pcap_rec for
+     * every packet its interface sends (after the packet went to the router
+     * or the loopback task, :571-574) and receives (after its socket processed
+     * it, :415-418; the loopback delivery too) into that host's ring of
+     * pcap_ring records in device memory (0: 65 536); the rings exist for the
+     * capture hosts only, and a model with none allocates nothing and runs
+     * the rounds as before.  The rings are emptied into host memory between
+     * batches of rounds (shd_tcp_run: after every batch of 64; a group: after
+     * 64 rounds at the latest, or once a ring is past half), so a capture is
+     * as long as the run; a ring that fills between two drains sets
+     * SHD_TCP_ERR_PCAP.  Capture works with and without trace.  The
+     * reference's capture reads every packet's TCP header and asserts on a
+     * datagram (network_interface.c:348, packet.c:485-489): a model with a
+     * capture host and a datagram process is refused (-22). */
+    const uint8_t* pcap_host;
+    uint32_t pcap_ring, _pad10;
 } shd_tcp_model;
+
+/* one captured packet: what _networkinterface_capturePacket takes from the
+ * packet's TCP header (addresses and ports in host byte order here), the time
+ * it was captured and the direction; shd_pcap_format makes the file's bytes */
+typedef struct shd_pcap_rec {
+    uint64_t time;                    /* ns */
+    uint32_t src_ip, dst_ip;
+    uint32_t seq, ack, win;           /* as the packet holds them (ack also when ACK is clear) */
+    uint16_t src_port, dst_port;
+    uint16_t len;                     /* payload bytes */
+    uint8_t flags;                    /* SHD_PCAP_RST | _SYN | _ACK | _FIN */
+    uint8_t dir;                      /* SHD_PCAP_IN / SHD_PCAP_OUT */
+    uint32_t _pad;
+} shd_pcap_rec;
+enum { SHD_PCAP_RST = 1, SHD_PCAP_SYN = 2, SHD_PCAP_ACK = 4, SHD_PCAP_FIN = 8 };
+enum { SHD_PCAP_IN = 0, SHD_PCAP_OUT = 1 };
 
 /* the first path query a host made of a vertex pair (topology_isRoutable /
  * getLatency / getReliability): the executing event's key (event_compare:
@@ -147,6 +181,16 @@ typedef struct shd_tcp_result {
      * node_counters, n_heartbeats) and the lines are these hosts'; the lines
      * carry the model's host index.  queries: every engine's. */
     int32_t first_host, n_local_hosts;
+    /* the capture records of this result's hosts (shd_tcp_model.pcap_host):
+     * hosts in index order, each host's records in its interface's order;
+     * host first_host + i's are pcap_records[pcap_off[i] .. pcap_off[i + 1]).
+     * NULL / NULL when the model has no capture host.  pcap_drains: the times
+     * the rings were emptied with something in them; pcap_ring_peak: the most
+     * records one host's ring held at a drain. */
+    shd_pcap_rec* pcap_records;
+    uint64_t* pcap_off;               /* [n_local_hosts + 1] */
+    uint64_t pcap_drains;
+    uint32_t pcap_ring_peak, _pad11;
 } shd_tcp_result;
 
 /* shd_tcp_run's `trace` bits */
@@ -155,7 +199,8 @@ enum { SHD_TCP_TRACE_STATUS = 1, SHD_TCP_TRACE_NODE = 2 };
 enum {
     SHD_TCP_ERR_EVQ = 1, SHD_TCP_ERR_POOL = 2, SHD_TCP_ERR_QUEUE = 4, SHD_TCP_ERR_SOCKETS = 8,
     SHD_TCP_ERR_MAILBOX = 16, SHD_TCP_ERR_TRACE = 32, SHD_TCP_ERR_SACK = 64, SHD_TCP_ERR_INTERNAL = 128,
-    SHD_TCP_ERR_QLOG = 256, SHD_TCP_ERR_FIRST_TOUCH = 512
+    SHD_TCP_ERR_QLOG = 256, SHD_TCP_ERR_FIRST_TOUCH = 512,
+    SHD_TCP_ERR_PCAP = 1024   /* a capture ring filled between two drains (pcap_ring) */
 };
 
 /* Run the model to end_time on the current HIP device (the reference's
@@ -165,7 +210,7 @@ enum {
  * -22 an invalid model, -113 a client whose server has no route in either
  * direction (the reference's connect fails with ECONNREFUSED there,
  * host.c:1224-1234; the device application has no such branch), -12 no device
- * memory for the trace buffers, -5 a HIP error.  A client on another host than
+ * memory for the trace buffers or the capture rings, -5 a HIP error.  A client on another host than
  * its server that starts less than one window W (the smallest path latency)
  * after it is refused (-22): it could connect in the round its server binds,
  * and the port it reads would depend on the lanes' timing.  *out is allocated by the call
@@ -211,6 +256,35 @@ int shd_tcp_run_group(const shd_tcp_model* m, struct shd_comm* comm, int32_t tra
  * 0 (the default): release them now and after every call.  A caller that runs
  * many models in one process (a parameter sweep, the bench) sets 1. */
 void shd_tcp_keep_workspace(int32_t keep);
+
+/* The pcap files of captured hosts (utility/pcap_writer.c:19-137 restated
+ * byte for byte; plain C, no device).  A file is the 24-byte global header
+ * (0xA1B2C3D4, 2, 4, 0, 0, 65535, 1 in host byte order) and per record:
+ * ts_sec = t / 10^9, ts_usec = (t % 10^9) / 1000, incl_len = orig_len = 66 +
+ * payload; 14 Ethernet bytes (the two fixed MACs, 08 00); 20 IP bytes (45 00,
+ * htons(orig_len - 14), 00 00, 40 00, 64, 6, 00 00, the addresses in network
+ * order); 32 TCP bytes (the ports in network order, htonl(seq), htonl(ack)
+ * when ACK is set and 0 otherwise, 80, the flag byte, htons((uint16_t)win),
+ * 00 00, 14 zero bytes); the payload.  win is cut to 16 bits as the
+ * reference's cast cuts it (network_interface.c:360-361).  The engine
+ * simulates lengths, not content: payload bytes are zeros.
+ * SHD_PCAP_HEADERS_ONLY: incl_len = 66, orig_len unchanged, no payload bytes.
+ *
+ * shd_pcap_format: the header (when with_header != 0) and the n records into
+ * buf; returns the bytes needed, and writes only when cap holds them all
+ * (buf NULL / cap 0: the size alone).
+ * shd_pcap_write_host: writes <dir>/<hostname>-<a.b.c.d>.pcap
+ * (network_interface.c:641-647; ip in host byte order) with the records, and
+ * the host's loopback interface file <dir>/<hostname>-127.0.0.1.pcap with the
+ * global header only (no model binds 127.0.0.1).  dir NULL: "data/pcapdata/"
+ * (pcap_writer.c:150-153); the directory must exist.  Returns 0, -22 for
+ * missing arguments, -2 when a file cannot be opened (the reference only
+ * warns), -5 when a write fails. */
+enum { SHD_PCAP_HEADERS_ONLY = 1 };
+size_t shd_pcap_format(const shd_pcap_rec* recs, uint64_t n, uint32_t flags, int32_t with_header, uint8_t* buf,
+                       size_t cap);
+int shd_pcap_write_host(const char* dir, const char* hostname, uint32_t ip, const shd_pcap_rec* recs, uint64_t n,
+                        uint32_t flags);
 
 #ifdef __cplusplus
 }

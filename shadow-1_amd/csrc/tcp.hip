@@ -354,6 +354,14 @@ struct Glob {
     int32_t world, me;
     uint32_t xcap, xsack_cap;
     size_t xseg;            // bytes per segment
+    // packet capture (shd_tcp_model.pcap_host): pcap_on is the one value a
+    // capture point tests; the capture hosts' rings pcrec [n slots][pcap_ring], their
+    // fill counts (each written by its host's lane only) and each local host's
+    // slot (-1: not captured).  All null with no capture host.
+    uint32_t pcap_on, pcap_ring;
+    shd_pcap_rec* pcrec;
+    uint32_t* npcap;
+    const int32_t* pcap_slot;   // [nloc]
 };
 struct XSegHead { uint32_t n, nsack, err, _pad[13]; };   // 64 B, then xcap Mails, then xsack_cap SACK words
 static_assert(sizeof(XSegHead) == 64, "segment header");
@@ -1714,6 +1722,34 @@ __device__ void tracker_add(L& c, int32_t pi, int dir) {
         else { t[0]++; t[1] += hdr; }
     }
 }
+// _networkinterface_capturePacket (network_interface.c:337-373) for a capture
+// host: the packet's header as it stands now into the host's ring.  The lane is
+// its ring's only writer (plain counter); a full ring fails the run, never
+// truncates (the rings are emptied between batches: tcp_run_impl).  Called
+// under Glob::pcap_on only, the branch marked unlikely: inlined on the fall-
+// through path the body cost a run with no capture host 1.4 % (23.38 against
+// 23.73 M events/s, with the hint 23.70; out of line it costs 4 B of scratch
+// -- profiles/pcap/ab.txt).
+__device__ void pcap_capture(L& c, int32_t pi, uint32_t dir) {
+    const Glob& g = *c.g;
+    const int32_t s = g.pcap_slot[c.h];
+    if (s < 0) return;
+    const uint32_t n = g.npcap[s];
+    if (n >= g.pcap_ring) { c.H->err |= SHD_TCP_ERR_PCAP; return; }
+    const DPkt* p = PK(c, pi);
+    shd_pcap_rec r;
+    r.time = c.now;
+    r.src_ip = p->sip; r.dst_ip = p->dip;
+    r.seq = p->seq; r.ack = p->ack; r.win = p->win;
+    r.src_port = p->sport; r.dst_port = p->dport;
+    r.len = (uint16_t)p->len;
+    r.flags = (uint8_t)(((p->flags & F_RST) ? SHD_PCAP_RST : 0) | ((p->flags & F_SYN) ? SHD_PCAP_SYN : 0) |
+                        ((p->flags & F_ACK) ? SHD_PCAP_ACK : 0) | ((p->flags & F_FIN) ? SHD_PCAP_FIN : 0));
+    r.dir = (uint8_t)dir;
+    r._pad = 0;
+    g.pcrec[(size_t)s * g.pcap_ring + n] = r;
+    g.npcap[s] = n + 1;
+}
 __device__ void if_receive_packet(L& c, int32_t pi) {   // _networkinterface_receivePacket (:375-419)
     const DPkt* p = PK(c, pi);
     pkt_status(c, pi, S_RCV_INTERFACE_RECEIVED);
@@ -1729,6 +1765,7 @@ __device__ void if_receive_packet(L& c, int32_t pi) {   // _networkinterface_rec
         pkt_status(c, pi, S_RCV_INTERFACE_DROPPED);
     }
     tracker_add(c, pi, 0);   // :415
+    if (__builtin_expect(c.g->pcap_on != 0, 0)) pcap_capture(c, pi, SHD_PCAP_IN);   // :416-418
 }
 __device__ void if_receive_packets(L& c) {   // :421-455
     DHost* H = c.H;
@@ -1877,6 +1914,7 @@ __device__ void if_send_packets(L& c) {   // :519-579, FIFO qdisc
         consume(H->tx_rem, (uint64_t)PK(c, pi)->len + hdr_of(PK(c, pi)));
         refill_if_needed(c);
         tracker_add(c, pi, 1);   // :571
+        if (__builtin_expect(c.g->pcap_on != 0, 0)) pcap_capture(c, pi, SHD_PCAP_OUT);   // :572-574
         pkt_unref(c, pi);
         if (drained) udp_release(c, drained);
     }
@@ -3016,7 +3054,7 @@ enum WsSlot {
     kWsHostProcs, kWsPool, kWsPsack, kWsFreel, kWsEv, kWsCq, kWsMsack, kWsNmsack, kWsMail, kWsNmail, kWsMhead,
     kWsMnext, kWsCtl, kWsIpk, kWsNode, kWsTr, kWsTrs, kWsNextTime, kWsQlog, kWsNqlog, kWsProf, kWsProfRound,
     kWsAppSpec, kWsAppPeer, kWsDestCum, kWsHostClass, kWsIpAll, kWsBwu, kWsBwd, kWsProcPort, kWsPortNew, kWsXsend,
-    kWsXrecv, kWsPmine, kWsPall, kWsXcnt, kWsGmine, kWsGall, kWsSlots
+    kWsXrecv, kWsPmine, kWsPall, kWsXcnt, kWsGmine, kWsGall, kWsPcap, kWsNpcap, kWsPcapSlot, kWsSlots
 };
 struct TcpWs {
     std::mutex mu;
@@ -3082,6 +3120,42 @@ struct TcpSched {
     std::vector<int32_t> v;
     bool extended = false;
 };
+// the capture hosts' records on the host side (shd_tcp_model.pcap_host): one
+// list per capture slot, grown by the drains.  A rerun from the start
+// (TcpSched) is a new call of tcp_run_impl and starts with empty lists.
+constexpr uint32_t kPcapRing = 1u << 16;   // records per capture host's ring by default
+struct TcpPcap {
+    std::vector<int32_t> host;                       // slot -> the host's index on this engine
+    std::vector<uint32_t> cnt;                       // the rings' fill counts as last copied
+    std::vector<std::vector<shd_pcap_rec>> recs;     // slot -> its records so far
+    uint64_t drains = 0, rounds_since = 0;
+    uint32_t peak = 0;
+};
+// the used part of every non-empty ring (pc.cnt: the counts just copied) to
+// host memory and the counts back to zero, on the run's stream: a ring never
+// carries records from one drain to the next
+static hipError_t pcap_drain(TcpPcap& pc, const Glob& g, hipStream_t st) {
+    bool any = false;
+    pc.rounds_since = 0;
+    for (size_t s = 0; s < pc.cnt.size(); s++) {
+        const uint32_t n = std::min(pc.cnt[s], g.pcap_ring);
+        if (!n) continue;
+        any = true;
+        pc.peak = std::max(pc.peak, n);
+        std::vector<shd_pcap_rec>& v = pc.recs[s];
+        const size_t at = v.size();
+        v.resize(at + n);
+        const hipError_t e = hipMemcpyAsync(v.data() + at, g.pcrec + s * (size_t)g.pcap_ring, sizeof(shd_pcap_rec) * n,
+                                            hipMemcpyDeviceToHost, st);
+        if (e != hipSuccess) return e;
+    }
+    if (!any) return hipSuccess;
+    pc.drains++;
+    const hipError_t e = hipMemsetAsync(g.npcap, 0, sizeof(uint32_t) * pc.cnt.size(), st);
+    if (e != hipSuccess) return e;
+    return hipStreamSynchronize(st);
+}
+
 static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, shd_tcp_result** out,
                         TcpSched* sch = nullptr) {
     const auto t_call = std::chrono::steady_clock::now();
@@ -3125,6 +3199,12 @@ static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, s
         if (m->host_class && m->n_classes > 1)
             for (int32_t a = 0; a < H; a++) if (m->host_class[a] >= m->n_classes) return -22;
     }
+    // packet capture reads every packet's TCP header (network_interface.c:348):
+    // the reference asserts on a datagram there, so such a model is refused
+    bool any_pcap = false;
+    if (m->pcap_host)
+        for (int32_t a = 0; a < H; a++) any_pcap |= m->pcap_host[a] != 0;
+    if (any_pcap && (any_udp || m->pcap_ring > (1u << 24))) return -22;
     const int32_t V = pc ? pc->T : m->n_vertices;
     std::vector<int32_t> hvi(H);   // each host's table index: the given one, or its attached index in the cache
     for (int32_t a = 0; a < H; a++) {
@@ -3222,6 +3302,8 @@ static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, s
     std::vector<uint64_t> ipk;
     uint64_t rounds = 0;
     std::vector<DHost> hout(nloc);
+    TcpPcap pcp;
+    int32_t* d_pslot = nullptr;
     uint32_t* d_ipall = nullptr; uint64_t* d_bwu = nullptr; uint64_t* d_bwd = nullptr;
     uint32_t* d_sched = nullptr;   // the first-touch schedule (TcpSched), when it has entries
     char* d_xrecv = nullptr; uint64_t* d_pmine = nullptr; uint64_t* d_pall = nullptr; uint32_t* d_xcnt = nullptr;
@@ -3441,6 +3523,34 @@ static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, s
             goto done;
         }
     }
+    if (any_pcap) {   // a ring per capture host of this engine, by capture slot: nothing per model host but the slot
+        std::vector<int32_t> slot(nloc, -1);
+        for (int32_t i = 0; i < nloc; i++)
+            if (m->pcap_host[h0 + i]) {
+                slot[i] = (int32_t)pcp.host.size();
+                pcp.host.push_back(i);
+            }
+        const size_t ns = pcp.host.size();
+        if (ns) {
+            g.pcap_ring = m->pcap_ring ? m->pcap_ring : kPcapRing;
+            const size_t need = sizeof(shd_pcap_rec) * ns * (size_t)g.pcap_ring;
+            if (ws_alloc(ws, kWsPcap, &g.pcrec, need) != hipSuccess ||
+                ws_alloc(ws, kWsNpcap, &g.npcap, sizeof(uint32_t) * ns) != hipSuccess ||
+                ws_alloc(ws, kWsPcapSlot, &d_pslot, sizeof(int32_t) * (size_t)nloc) != hipSuccess) {
+                (void)hipGetLastError();
+                fprintf(stderr, "shd_tcp_run: no device memory for the capture rings of %zu hosts (%.1f GB); "
+                                "capture fewer hosts or set a smaller pcap_ring\n", ns, need / 1e9);
+                rc = -12;
+                goto done;
+            }
+            HCHECK(hipMemset(g.npcap, 0, sizeof(uint32_t) * ns));
+            HCHECK(hipMemcpy(d_pslot, slot.data(), sizeof(int32_t) * (size_t)nloc, hipMemcpyHostToDevice));
+            g.pcap_slot = d_pslot;
+            g.pcap_on = 1;
+            pcp.cnt.assign(ns, 0);
+            pcp.recs.resize(ns);
+        }
+    }
     HCHECK(ws_alloc(ws, kWsNextTime, &g.next_time, sizeof(uint64_t) * (nloc + 1)));
     HCHECK(hipMemset(g.next_time, 0xff, sizeof(uint64_t) * (nloc + 1)));
     // every host can log kPq first queries (touch_log)
@@ -3485,7 +3595,11 @@ static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, s
             if (world == 1) {
                 HCHECK(hipGraphLaunch(gexec, st));
                 HCHECK(hipMemcpyAsync(&hctl, g.ctl, sizeof(TCtl), hipMemcpyDeviceToHost, st));
+                if (g.pcap_on)   // the batch's captures: the counts with the control word, then the rings' used parts
+                    HCHECK(hipMemcpyAsync(pcp.cnt.data(), g.npcap, sizeof(uint32_t) * pcp.cnt.size(),
+                                          hipMemcpyDeviceToHost, st));
                 HCHECK(hipStreamSynchronize(st));
+                if (g.pcap_on) HCHECK(pcap_drain(pcp, g, st));
             } else {
                 // a group's round (slave.c:437-462 across engines): the earliest
                 // event over the group opens the window; the round's ports and
@@ -3586,12 +3700,25 @@ static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, s
                 }
                 HCHECK(hipGetLastError());
                 HCHECK(hipMemcpyAsync(&hctl, g.ctl, sizeof(TCtl), hipMemcpyDeviceToHost, st));
+                if (g.pcap_on)
+                    HCHECK(hipMemcpyAsync(pcp.cnt.data(), g.npcap, sizeof(uint32_t) * pcp.cnt.size(),
+                                          hipMemcpyDeviceToHost, st));
                 HCHECK(hipStreamSynchronize(st));
+                if (g.pcap_on) {   // a drain every 64 rounds at the latest, or once a ring is past half
+                    bool due = ++pcp.rounds_since >= 64;
+                    for (uint32_t n : pcp.cnt) due |= n > g.pcap_ring / 2;
+                    if (due) HCHECK(pcap_drain(pcp, g, st));
+                }
             }
             if (hctl.halted) break;
             if (hctl.rounds > (1ull << 26)) { res->error |= SHD_TCP_ERR_INTERNAL; break; }
         }
         rounds = hctl.rounds;
+        if (g.pcap_on) {   // what the rings hold since the last drain (a group's last rounds)
+            HCHECK(hipMemcpyAsync(pcp.cnt.data(), g.npcap, sizeof(uint32_t) * pcp.cnt.size(), hipMemcpyDeviceToHost, st));
+            HCHECK(hipStreamSynchronize(st));
+            HCHECK(pcap_drain(pcp, g, st));
+        }
         HCHECK(hipEventRecord(e1, st));
         HCHECK(hipEventSynchronize(e1));
         float ms = 0;
@@ -3631,6 +3758,24 @@ static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, s
     res->next_packet_id = (uint64_t*)calloc(nloc, sizeof(uint64_t));
     res->rng_probe = (uint32_t*)calloc(nloc, sizeof(uint32_t));
     res->rounds = rounds;
+    if (any_pcap) {   // the capture hosts' records, hosts in index order (the slots' order)
+        res->pcap_off = (uint64_t*)calloc((size_t)nloc + 1, sizeof(uint64_t));
+        size_t tot = 0;
+        for (const auto& v : pcp.recs) tot += v.size();
+        res->pcap_records = (shd_pcap_rec*)malloc(sizeof(shd_pcap_rec) * (tot ? tot : 1));
+        size_t o = 0, s = 0;
+        for (int32_t i = 0; i < nloc; i++) {
+            res->pcap_off[i] = o;
+            if (s < pcp.host.size() && pcp.host[s] == i) {
+                if (!pcp.recs[s].empty())
+                    memcpy(res->pcap_records + o, pcp.recs[s].data(), sizeof(shd_pcap_rec) * pcp.recs[s].size());
+                o += pcp.recs[s++].size();
+            }
+        }
+        res->pcap_off[nloc] = o;
+        res->pcap_drains = pcp.drains;
+        res->pcap_ring_peak = pcp.peak;
+    }
     {   // the last two rounds' mailboxes were never counted by k_tcp_window
         std::vector<uint32_t> nm(2 * (kMailSub + 1));
         HCHECK(hipMemcpy(nm.data(), g.nmail, sizeof(uint32_t) * nm.size(), hipMemcpyDeviceToHost));
@@ -3794,5 +3939,7 @@ extern "C" void shd_tcp_result_free(shd_tcp_result* r) {
     free(r->queries);
     free(r->node_counters);
     free(r->n_heartbeats);
+    free(r->pcap_records);
+    free(r->pcap_off);
     free(r);
 }

@@ -61,7 +61,7 @@ void shd_config_free(shd_config* c) {
     for (int32_t i = 0; i < c->n_hosts; i++) {
         shd_config_host* h = &c->hosts[i];
         free(h->name); free(h->ip_hint); free(h->citycode_hint); free(h->countrycode_hint);
-        free(h->geocode_hint); free(h->type_hint); free(h->process_start_s);
+        free(h->geocode_hint); free(h->type_hint); free(h->process_start_s); free(h->pcapdir);
     }
     free(c->hosts);
     free(c->topology_path);
@@ -125,6 +125,8 @@ static int parse_doc(xmlDocPtr doc, shd_config** out) {
             char* bd = attr_ci(n, "bandwidthdown");
             char* bu = attr_ci(n, "bandwidthup");
             char* hb = attr_ci(n, "heartbeatfrequency");
+            char* lp = attr_ci(n, "logpcap");
+            char* pd = attr_ci(n, "pcapdir");
             /* the host's processes in document order: their start times */
             int32_t np = 0;
             uint64_t* starts = NULL;
@@ -157,6 +159,8 @@ static int parse_doc(xmlDocPtr doc, shd_config** out) {
                 h.bw_down_kibps = to_u64(bd);
                 h.bw_up_kibps = to_u64(bu);
                 h.heartbeat_s = to_u64(hb);
+                h.logpcap = (lp && !strcasecmp(lp, "true")) ? 1 : 0;   /* master.c:352 */
+                h.pcapdir = dup_str(pd);
                 h.n_processes = np;
                 if (np) {
                     h.process_start_s = (uint64_t*)malloc(sizeof(uint64_t) * (size_t)np);
@@ -167,6 +171,7 @@ static int parse_doc(xmlDocPtr doc, shd_config** out) {
             }
             free(starts);
             free(id); free(iph); free(cch); free(coh); free(geh); free(tyh); free(bd); free(bu); free(hb);
+            free(lp); free(pd);
         }
     }
     if (rc != SHD_OK) {

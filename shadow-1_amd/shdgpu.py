@@ -34,7 +34,7 @@ TR_SENT, TR_INET_DROP, TR_ARRIVE, TR_CODEL_DROP, TR_RECV, TR_IF_DROP, TR_LOCAL, 
 
 ERRORS = {
     0: "ok", -22: "EINVAL", -12: "ENOMEM", -19: "ENODEV", -75: "EOVERFLOW",
-    -34: "ERANGE", -125: "EAMBIG", -107: "ENOTCONN",
+    -34: "ERANGE", -125: "EAMBIG", -107: "ENOTCONN", -2: "ENOENT", -5: "EIO",
 }
 
 
@@ -70,7 +70,8 @@ class ConfigHost(C.Structure):
     _fields_ = [("name", C.c_char_p), ("ip_hint", C.c_char_p), ("citycode_hint", C.c_char_p),
                 ("countrycode_hint", C.c_char_p), ("geocode_hint", C.c_char_p), ("type_hint", C.c_char_p),
                 ("bw_down_kibps", C.c_uint64), ("bw_up_kibps", C.c_uint64), ("heartbeat_s", C.c_uint64),
-                ("n_processes", C.c_int32), ("_pad", C.c_int32), ("process_start_s", C.POINTER(C.c_uint64))]
+                ("n_processes", C.c_int32), ("logpcap", C.c_int32), ("process_start_s", C.POINTER(C.c_uint64)),
+                ("pcapdir", C.c_char_p)]
 
 
 class Config(C.Structure):
@@ -204,7 +205,8 @@ class TcpModel(C.Structure):
                 ("_pad", C.c_uint32), ("path_cache", C.c_void_p),
                 ("proc_app", P(C.c_int32)), ("app_spec", P(C.c_uint32)), ("n_app_specs", C.c_int32),
                 ("udp_payload", C.c_uint32), ("app_peer", P(C.c_int32)), ("dest_cum", P(C.c_double)),
-                ("host_class", P(C.c_uint8)), ("n_classes", C.c_int32), ("_pad2", C.c_int32)]
+                ("host_class", P(C.c_uint8)), ("n_classes", C.c_int32), ("_pad2", C.c_int32),
+                ("pcap_host", P(C.c_uint8)), ("pcap_ring", C.c_uint32), ("_pad10", C.c_uint32)]
 
 
 class TcpResult(C.Structure):
@@ -217,11 +219,23 @@ class TcpResult(C.Structure):
                 ("node_counters", P(C.c_uint64)), ("n_heartbeats", P(C.c_uint32)), ("node_k", C.c_uint32),
                 ("first_touch_reruns", C.c_uint32), ("max_round_deliveries", C.c_uint64), ("max_round_overflow", C.c_uint64),
                 ("setup_ms", C.c_double), ("results_ms", C.c_double), ("teardown_ms", C.c_double),
-                ("first_host", C.c_int32), ("n_local_hosts", C.c_int32)]
+                ("first_host", C.c_int32), ("n_local_hosts", C.c_int32),
+                ("pcap_records", C.c_void_p), ("pcap_off", P(C.c_uint64)), ("pcap_drains", C.c_uint64),
+                ("pcap_ring_peak", C.c_uint32), ("_pad11", C.c_uint32)]
 
 
 TCP_TRACE_STATUS, TCP_TRACE_NODE = 1, 2   # shd_tcp_run's trace bits
 TCP_ERR_FIRST_TOUCH = 512                  # SHD_TCP_ERR_FIRST_TOUCH (include/shdtcp.h)
+TCP_ERR_PCAP = 1024                        # SHD_TCP_ERR_PCAP: a capture ring filled between two drains
+
+# shd_pcap_rec (include/shdtcp.h): one captured packet; addresses and ports in host byte order
+PCAP_DTYPE = np.dtype([("time", "<u8"), ("src_ip", "<u4"), ("dst_ip", "<u4"), ("seq", "<u4"), ("ack", "<u4"),
+                       ("win", "<u4"), ("src_port", "<u2"), ("dst_port", "<u2"), ("len", "<u2"), ("flags", "u1"),
+                       ("dir", "u1"), ("_pad", "<u4")])
+assert PCAP_DTYPE.itemsize == 40
+PCAP_RST, PCAP_SYN, PCAP_ACK, PCAP_FIN = 1, 2, 4, 8   # shd_pcap_rec.flags
+PCAP_IN, PCAP_OUT = 0, 1                               # shd_pcap_rec.dir
+PCAP_HEADERS_ONLY = 1                                  # shd_pcap_format / shd_pcap_write_host flags
 
 
 TCP_QUERY_DTYPE = np.dtype([("time", "<u8"), ("seq", "<u8"), ("host", "<u4"), ("src", "<u4"), ("index", "<u4"),
@@ -240,6 +254,8 @@ _SIGS = {
     "shd_tcp_run_group": (C.c_int, [P(TcpModel), C.c_void_p, C.c_int32, P(P(TcpResult))]),
     "shd_tcp_result_free": (None, [P(TcpResult)]),
     "shd_tcp_keep_workspace": (None, [C.c_int32]),
+    "shd_pcap_format": (C.c_size_t, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int32, C.c_void_p, C.c_size_t]),
+    "shd_pcap_write_host": (C.c_int, [C.c_char_p, C.c_char_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32]),
     "shd_tracker_node_lines": (C.c_int, [P(C.c_uint64), C.c_uint64, C.c_uint64, C.c_uint32, P(P(Lines))]),
     "shd_graph_check": (C.c_int, [P(Graph), P(GraphProps)]),
     "shd_graphml_load_file": (C.c_int, [C.c_char_p, P(P(GraphML))]),
@@ -413,7 +429,7 @@ def load_config(xml: bytes):
         hosts = [dict(name=dec(h.name), ip_hint=dec(h.ip_hint), citycode_hint=dec(h.citycode_hint),
                       countrycode_hint=dec(h.countrycode_hint), geocode_hint=dec(h.geocode_hint),
                       type_hint=dec(h.type_hint), bw_down_kibps=h.bw_down_kibps, bw_up_kibps=h.bw_up_kibps,
-                      heartbeat_s=h.heartbeat_s,
+                      heartbeat_s=h.heartbeat_s, logpcap=bool(h.logpcap), pcapdir=dec(h.pcapdir),
                       process_start_s=[h.process_start_s[k] for k in range(h.n_processes)])
                  for h in (c.hosts[i] for i in range(c.n_hosts))]
         ips = np.zeros(max(c.n_hosts, 1), dtype=np.uint32)
@@ -422,6 +438,38 @@ def load_config(xml: bytes):
         return hosts, ips[:c.n_hosts], c.stop_time_s, topo
     finally:
         lib().shd_config_free(ptr)
+
+
+def pcap_bytes(records, flags: int = 0, header: bool = True) -> bytes:
+    """The pcap file bytes of one host's capture records (PCAP_DTYPE), from the
+    library's writer (shd_pcap_format): the global header when `header`, then
+    one record per packet."""
+    r = np.ascontiguousarray(np.asarray(records, dtype=PCAP_DTYPE))
+    ptr = r.ctypes.data if len(r) else None
+    need = lib().shd_pcap_format(ptr, len(r), int(flags), int(header), None, 0)
+    buf = C.create_string_buffer(max(int(need), 1))
+    got = lib().shd_pcap_format(ptr, len(r), int(flags), int(header), buf, need)
+    assert got == need
+    return buf.raw[:need]
+
+
+def write_pcap_files(pcap_records, names, ips, directory=None, flags: int = 0) -> list:
+    """Write the pcap files of every captured host (shd_pcap_write_host):
+    pcap_records {host index: records} as tcp.run(..., pcap=...) returns them,
+    names / ips the model's host names and host-order addresses.  Per host
+    <directory>/<name>-<a.b.c.d>.pcap and the header-only loopback file
+    <name>-127.0.0.1.pcap, as the reference's two interfaces write them;
+    directory None: data/pcapdata/.  The directory must exist; a file that
+    cannot be opened raises.  Returns the capture files' paths."""
+    d = None if directory is None else os.fsencode(directory)
+    out = []
+    for h in sorted(pcap_records):
+        r = np.ascontiguousarray(np.asarray(pcap_records[h], dtype=PCAP_DTYPE))
+        check(lib().shd_pcap_write_host(d, names[h].encode(), int(ips[h]), r.ctypes.data if len(r) else None, len(r),
+                                        int(flags)), f"shd_pcap_write_host({names[h]})")
+        base = "data/pcapdata/" if directory is None else os.fspath(directory)
+        out.append(os.path.join(base, "%s-%s.pcap" % (names[h], ip_str(ips[h]))))
+    return out
 
 
 def ip_str(ip: int) -> str:

@@ -100,7 +100,7 @@ def serial_first_queries(queries: np.ndarray):
 
 def run(model: S.ModelArrays, g: S.GraphArrays, ips, procs, peers, nbytes=20000, trace=True,
         recv_buf=RECV_BUF, send_buf=SEND_BUF, tcp_window=TCP_WINDOW, packets_per_host=0, guess_reversed=False,
-        node=False, qdisc=0, mode="device", udp=None, comm=None):
+        node=False, qdisc=0, mode="device", udp=None, comm=None, pcap=None):
     """Run the TCP echo model on the GPU: procs = [(host, start ns)], peers =
     [-1 | server process]; ips: host-order uint32 per host.  Returns
     dict(lines=[(t, h, line)] in each host's order, next_event_id,
@@ -120,7 +120,13 @@ def run(model: S.ModelArrays, g: S.GraphArrays, ips, procs, peers, nbytes=20000,
     rank calls with the same model; the result covers hosts [first_host,
     first_host + n_local_hosts), the lines carry the model's host index); every
     rank's first touches are ranked together, on the device (each round's logs
-    gathered) or over the tables' query logs."""
+    gathered) or over the tables' query logs.
+    pcap: dict(hosts=[host indices], ring=0) -- packet capture on those hosts
+    (shd_tcp_model.pcap_host; ring: records per host's device ring, 0 = 65 536),
+    with or without trace.  The result then has pcap_records {host index:
+    S.PCAP_DTYPE array in the interface's order} for the captured hosts the
+    result covers, pcap_drains and pcap_ring_peak; S.write_pcap_files makes
+    the files."""
     if mode == "device" and not guess_reversed and not g.directed:
         m = model.struct
         H = int(m.n_hosts)
@@ -130,7 +136,8 @@ def run(model: S.ModelArrays, g: S.GraphArrays, ips, procs, peers, nbytes=20000,
         pc_ms = (time.perf_counter() - t_pc) * 1e3
         try:
             out = _run_once(model, ips, procs, peers, None, None, hv.astype(np.int32), nbytes, trace, recv_buf,
-                            send_buf, tcp_window, packets_per_host, node, qdisc, pc=pc, udp=udp, comm=comm)
+                            send_buf, tcp_window, packets_per_host, node, qdisc, pc=pc, udp=udp, comm=comm,
+                            pcap=pcap)
         finally:
             pc.close()
         if out is not None:
@@ -142,7 +149,7 @@ def run(model: S.ModelArrays, g: S.GraphArrays, ips, procs, peers, nbytes=20000,
     V = lat.shape[0]
     for runs in range(1, 9):
         out = _run_once(model, ips, procs, peers, lat, rel, hvi, nbytes, trace, recv_buf, send_buf, tcp_window,
-                        packets_per_host, node, qdisc, udp=udp, comm=comm)
+                        packets_per_host, node, qdisc, udp=udp, comm=comm, pcap=pcap)
         order, pairs = serial_first_queries(out.pop("queries"))
         lat2, rel2 = resolve(g, att, order, pairs, V)
         ij = tuple(np.array([(a, b) for a, b in pairs] + [(b, a) for a, b in pairs], dtype=np.int64).T) \
@@ -162,7 +169,7 @@ def run(model: S.ModelArrays, g: S.GraphArrays, ips, procs, peers, nbytes=20000,
 
 
 def _run_once(model, ips, procs, peers, lat, rel, hvi, nbytes, trace, recv_buf, send_buf, tcp_window,
-              packets_per_host, node=False, qdisc=0, pc=None, udp=None, comm=None):
+              packets_per_host, node=False, qdisc=0, pc=None, udp=None, comm=None, pcap=None):
     """one shd_tcp_run on the given path tables, or with pc (sim.PathCache) on
     the cache itself (hvi: graph vertices then); None when that run's
     first-touch choices were contradicted (SHD_TCP_ERR_FIRST_TOUCH)"""
@@ -210,6 +217,11 @@ def _run_once(model, ips, procs, peers, lat, rel, hvi, nbytes, trace, recv_buf, 
         tm.dest_cum = m.dest_cum
         tm.host_class = m.host_class
         tm.n_classes = m.n_classes
+    if pcap is not None:
+        keep["pc"] = np.zeros(H, dtype=np.uint8)
+        keep["pc"][np.asarray(list(pcap["hosts"]), dtype=np.int64)] = 1
+        tm.pcap_host = S.as_ptr(keep["pc"], C.c_uint8)
+        tm.pcap_ring = int(pcap.get("ring", 0))
     res = C.POINTER(S.TcpResult)()
     bits = (S.TCP_TRACE_STATUS if trace else 0) | (S.TCP_TRACE_NODE if node else 0)
     if comm is not None:
@@ -240,6 +252,13 @@ def _run_once(model, ips, procs, peers, lat, rel, hvi, nbytes, trace, recv_buf, 
                    queries=np.frombuffer(C.string_at(r.queries, int(r.n_queries) * S.TCP_QUERY_DTYPE.itemsize),
                                          dtype=S.TCP_QUERY_DTYPE).copy() if r.n_queries else
                    np.zeros(0, dtype=S.TCP_QUERY_DTYPE))
+        if pcap is not None:
+            off = np.ctypeslib.as_array(r.pcap_off, shape=(HL + 1,)).copy()
+            recs = np.frombuffer(C.string_at(r.pcap_records, int(off[-1]) * S.PCAP_DTYPE.itemsize),
+                                 dtype=S.PCAP_DTYPE).copy() if off[-1] else np.zeros(0, dtype=S.PCAP_DTYPE)
+            out["pcap_records"] = {h0 + i: recs[int(off[i]):int(off[i + 1])] for i in range(HL) if keep["pc"][h0 + i]}
+            out["pcap_drains"] = int(r.pcap_drains)
+            out["pcap_ring_peak"] = int(r.pcap_ring_peak)
         if node:
             k = int(r.node_k)
             cnt = np.ctypeslib.as_array(r.node_counters, shape=(HL * k * 20,)).reshape(HL, k, 20)
