@@ -9,7 +9,11 @@
  * conservative rounds on one GPU: one lane per host, a round is every event
  * before the window's end (the smallest path latency), deliveries cross hosts
  * through a mailbox between rounds.  Results equal the reference's serial loop
- * (tests/test_tcp_gpu.py against tests/golden/ref_tcp.json).
+ * (tests/test_tcp_gpu.py against tests/golden/ref_tcp.json).  A bootstrap
+ * period (<shadow bootstraptime>: no drops, no token buckets before its end)
+ * and per-host heartbeat intervals (<host heartbeatfrequency>) run as the
+ * reference's loop runs them (shd_tcp_model.bootstrap_end / host_heartbeat;
+ * tests/test_tcp_options_gpu.py against tests/golden/ref_tcp_options.json).
  *
  * The boundary is the same one shdgpu.h draws for the UDP path: plain
  * pointers and sizes, no torch types.  Path latency and reliability per host
@@ -106,6 +110,36 @@ typedef struct shd_tcp_model {
      * capture host and a datagram process is refused (-22). */
     const uint8_t* pcap_host;
     uint32_t pcap_ring, _pad10;
+    /* The bootstrap period (<shadow bootstraptime>, shd_model.bootstrap_end):
+     * ns, 0 for none.  worker_isBootstrapActive() is now < bootstrap_end
+     * (worker.c:462-466: strict, at the executing event's time), read once
+     * where each of these begins:
+     *   worker_sendPacket (worker.c:281-290): the reliability is queried and
+     *     the random draw taken as always (first touches and the RNG stream do
+     *     not change); the packet passes if bootstrapping || chance <=
+     *     reliability || payload == 0;
+     *   _networkinterface_receivePackets (network_interface.c:431-454): the
+     *     loop is while (bootstrapping || receive bucket >= MTU); while
+     *     bootstrapping the bucket is not consumed and no refill is scheduled
+     *     (the router queue still dequeues through CoDel);
+     *   _networkinterface_sendPackets (network_interface.c:522-569): the
+     *     loop's condition stays send bucket >= MTU, with no "bootstrapping ||";
+     *     only the consume and the refill scheduling are skipped, for the
+     *     loopback +1 ns task's packets too.  Tracker counters and capture run
+     *     as always.
+     * Refill events stop by themselves once the buckets are full and start
+     * again with the first consume after the period, which the hosts' event-ID
+     * counters show.  The same value on every rank of a group. */
+    uint64_t bootstrap_end;
+    /* [H] each host's own heartbeat interval in ns (<host heartbeatfrequency>,
+     * host.c's heartbeatInterval; shd_model.host_heartbeat), or NULL:
+     * heartbeat_interval for every host.  The tracker's boot line and each
+     * heartbeat (tracker.c:141, 566-611) then come at the host's own interval;
+     * the [node] line's first field is that interval in whole seconds (a
+     * 500 ms host prints 0).  A zero entry is refused (-22), as
+     * shd_eng_create refuses one.  node_k is sized from the smallest interval
+     * among the engine's hosts; a group's rank reads its hosts' slice. */
+    const uint64_t* host_heartbeat;
 } shd_tcp_model;
 
 /* one captured packet: what _networkinterface_capturePacket takes from the
@@ -161,8 +195,10 @@ typedef struct shd_tcp_result {
      * counted here as the reference counts them: remote, since tracker.c:223
      * and :255 call a packet local only when its address is 127.0.0.1, which
      * no model's sockets use, so the localhost counters are zero.
-     * n_heartbeats[h] of them are host h's.
-     * shd_tracker_node_lines (shdgpu.h) makes the [node] lines of a host. */
+     * n_heartbeats[h] of them are host h's, one per interval of that host's
+     * own (shd_tcp_model.host_heartbeat).
+     * shd_tracker_node_lines (shdgpu.h) makes the [node] lines of a host from
+     * them and the host's interval. */
     uint64_t* node_counters;
     uint32_t* n_heartbeats;
     uint32_t node_k;

@@ -362,6 +362,12 @@ struct Glob {
     shd_pcap_rec* pcrec;
     uint32_t* npcap;
     const int32_t* pcap_slot;   // [nloc]
+    // the bootstrap period (shd_tcp_model.bootstrap_end; worker_isBootstrapActive,
+    // worker.c:462-466: now < end, strict): one uniform word the three places
+    // below compare the event's time with (0: never true), and each local
+    // host's own heartbeat interval (null: hb for every host)
+    uint64_t boot_end;
+    const uint64_t* hb_host;    // [nloc]
 };
 struct XSegHead { uint32_t n, nsack, err, _pad[13]; };   // 64 B, then xcap Mails, then xsack_cap SACK words
 static_assert(sizeof(XSegHead) == 64, "segment header");
@@ -1769,15 +1775,21 @@ __device__ void if_receive_packet(L& c, int32_t pi) {   // _networkinterface_rec
 }
 __device__ void if_receive_packets(L& c) {   // :421-455
     DHost* H = c.H;
-    while (H->rx_rem >= kMTU) {
+    // bootstrapping (:431-433): the loop runs whatever the bucket holds, the
+    // bucket is not consumed and no refill is scheduled (:448-453); the router
+    // queue still dequeues through CoDel
+    const bool boot = c.now < c.g->boot_end;
+    while (boot || H->rx_rem >= kMTU) {
         CqEnt e;
         if (!cq_dequeue(c, e)) break;
         pkt_status(c, e.pkt, S_ROUTER_DEQUEUED);
         const uint64_t len = (uint64_t)PK(c, e.pkt)->len + hdr_of(PK(c, e.pkt));
         if_receive_packet(c, e.pkt);
         pkt_unref(c, e.pkt);
-        consume(H->rx_rem, len);
-        refill_if_needed(c);
+        if (!boot) {
+            consume(H->rx_rem, len);
+            refill_if_needed(c);
+        }
     }
 }
 // a delivery for another engine's host: its record (and SACK list) into that
@@ -1833,8 +1845,11 @@ __device__ void worker_send_packet(L& c, int32_t pi, DSock* ks) {   // worker.c:
             ks->pc_lat = lat; ks->pc_rel = rel;
         }
     }
+    // worker.c:281-290: the reliability was queried and the draw is taken as
+    // always (the first-touch log and the RNG stream do not change); while
+    // bootstrapping every packet passes
     const double chance = next_double(&c.H->rng);
-    if (chance <= rel || p->len == 0) {
+    if (chance <= rel || p->len == 0 || c.now < c.g->boot_end) {
         const uint64_t t = c.now + (uint64_t)ceil(lat * (double)kMs);
         pkt_status(c, pi, S_INET_SENT);
         const uint64_t seq = c.H->ev_seq++;   // event_new_ (the delivery's ID)
@@ -1875,6 +1890,10 @@ __device__ void worker_send_packet(L& c, int32_t pi, DSock* ks) {   // worker.c:
 __device__ void if_send_packets(L& c) {   // :519-579, FIFO qdisc
     DHost* H = c.H;
     const SockLess lt{&c};
+    // bootstrapping (:522): the loop's condition stays the bucket's alone (:525,
+    // unlike the receive loop's); only the consume and the refill scheduling
+    // are skipped (:558-563), for the loopback +1 ns task's packets too
+    const bool boot = c.now < c.g->boot_end;
     while (H->tx_rem >= kMTU) {
         int32_t pi = -1;
         DSock* ks = nullptr;   // the socket the packet came from
@@ -1911,8 +1930,10 @@ __device__ void if_send_packets(L& c) {   // :519-579, FIFO qdisc
         } else {
             worker_send_packet(c, pi, ks);
         }
-        consume(H->tx_rem, (uint64_t)PK(c, pi)->len + hdr_of(PK(c, pi)));
-        refill_if_needed(c);
+        if (!boot) {
+            consume(H->tx_rem, (uint64_t)PK(c, pi)->len + hdr_of(PK(c, pi)));
+            refill_if_needed(c);
+        }
         tracker_add(c, pi, 1);   // :571
         if (__builtin_expect(c.g->pcap_on != 0, 0)) pcap_capture(c, pi, SHD_PCAP_OUT);   // :572-574
         pkt_unref(c, pi);
@@ -2347,7 +2368,7 @@ __device__ void execute(L& c, const DEv& e) {
             H->nhb++;
             for (uint32_t j = 0; j < 2 * kTrk; j++) H->trk[j] = 0;
         }
-        sched_task(c, c.g->hb, K_HEARTBEAT, -1);
+        sched_task(c, c.g->hb_host ? c.g->hb_host[c.h] : c.g->hb, K_HEARTBEAT, -1);   // the host's own interval (host.c)
         break;
     case K_REFILL: refill_cb(c); break;
     case K_REFILL_LO: break;
@@ -2453,7 +2474,7 @@ __global__ void __launch_bounds__(64) k_tcp_boot(Glob g) {
     if (h >= g.nloc) return;
     Glob gl = g;
     L c{&gl, h, gl.h0 + h, &gl.host[h], 0, h, 0, 0, 0, ~0ull};
-    sched_task(c, gl.hb, K_HEARTBEAT, -1);
+    sched_task(c, gl.hb_host ? gl.hb_host[h] : gl.hb, K_HEARTBEAT, -1);
     refill_cb(c);
     sched_task(c, kMs, K_REFILL_LO, -1);
     for (int j = 0; j < kProcs; j++) {
@@ -3054,7 +3075,7 @@ enum WsSlot {
     kWsHostProcs, kWsPool, kWsPsack, kWsFreel, kWsEv, kWsCq, kWsMsack, kWsNmsack, kWsMail, kWsNmail, kWsMhead,
     kWsMnext, kWsCtl, kWsIpk, kWsNode, kWsTr, kWsTrs, kWsNextTime, kWsQlog, kWsNqlog, kWsProf, kWsProfRound,
     kWsAppSpec, kWsAppPeer, kWsDestCum, kWsHostClass, kWsIpAll, kWsBwu, kWsBwd, kWsProcPort, kWsPortNew, kWsXsend,
-    kWsXrecv, kWsPmine, kWsPall, kWsXcnt, kWsGmine, kWsGall, kWsPcap, kWsNpcap, kWsPcapSlot, kWsSlots
+    kWsXrecv, kWsPmine, kWsPall, kWsXcnt, kWsGmine, kWsGall, kWsPcap, kWsNpcap, kWsPcapSlot, kWsHostHb, kWsSlots
 };
 struct TcpWs {
     std::mutex mu;
@@ -3205,6 +3226,11 @@ static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, s
     if (m->pcap_host)
         for (int32_t a = 0; a < H; a++) any_pcap |= m->pcap_host[a] != 0;
     if (any_pcap && (any_udp || m->pcap_ring > (1u << 24))) return -22;
+    // each host's own heartbeat interval (host.c's heartbeatInterval): a zero
+    // entry is refused, as shd_model.host_heartbeat's is (shd_eng_create)
+    if (m->host_heartbeat)
+        for (int32_t a = 0; a < H; a++)
+            if (m->host_heartbeat[a] == 0) return -22;
     const int32_t V = pc ? pc->T : m->n_vertices;
     std::vector<int32_t> hvi(H);   // each host's table index: the given one, or its attached index in the cache
     for (int32_t a = 0; a < H; a++) {
@@ -3304,6 +3330,8 @@ static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, s
     std::vector<DHost> hout(nloc);
     TcpPcap pcp;
     int32_t* d_pslot = nullptr;
+    uint64_t* d_hbh = nullptr;
+    uint64_t hb_min = 0;   // the smallest heartbeat interval among this engine's hosts (node_k)
     uint32_t* d_ipall = nullptr; uint64_t* d_bwu = nullptr; uint64_t* d_bwd = nullptr;
     uint32_t* d_sched = nullptr;   // the first-touch schedule (TcpSched), when it has entries
     char* d_xrecv = nullptr; uint64_t* d_pmine = nullptr; uint64_t* d_pall = nullptr; uint32_t* d_xcnt = nullptr;
@@ -3353,6 +3381,12 @@ static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, s
     g.H = H; g.P = P; g.W = W;
     g.h0 = h0; g.nloc = nloc; g.world = world; g.me = me;
     g.end_time = m->end_time; g.hb = m->heartbeat_interval ? m->heartbeat_interval : kSec;
+    g.boot_end = m->bootstrap_end;   // the same on every rank of a group
+    hb_min = g.hb;
+    if (m->host_heartbeat) {   // this engine's slice
+        hb_min = ~0ull;
+        for (int32_t i = 0; i < nloc; i++) hb_min = std::min<uint64_t>(hb_min, m->host_heartbeat[h0 + i]);
+    }
     g.tcp_bytes = m->tcp_bytes; g.trace = (trace & SHD_TCP_TRACE_STATUS) ? 1 : 0;
     g.recv_buf = m->recv_buf; g.send_buf = m->send_buf; g.tcp_window = m->tcp_window;
     if (m->qdisc > 1) { free(res); return -22; }
@@ -3502,7 +3536,7 @@ static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, s
     HCHECK(hipMemcpy(d_ipk, ipk.data(), sizeof(uint64_t) * ipk.size(), hipMemcpyHostToDevice));
     g.ip_key = d_ipk;
     if (trace & SHD_TCP_TRACE_NODE) {   // every heartbeat before the end, per host
-        g.node_k = (uint32_t)((m->end_time - 1) / g.hb) + 1;
+        g.node_k = (uint32_t)((m->end_time - 1) / hb_min) + 1;
         if (ws_alloc(ws, kWsNode, &g.node, sizeof(uint64_t) * 2 * kTrk * (size_t)nloc * g.node_k) != hipSuccess) {
             (void)hipGetLastError();
             fprintf(stderr, "shd_tcp_run: no device memory for the tracker counters\n");
@@ -3522,6 +3556,16 @@ static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, s
             rc = -12;
             goto done;
         }
+    }
+    if (m->host_heartbeat) {
+        if (ws_alloc(ws, kWsHostHb, &d_hbh, sizeof(uint64_t) * (size_t)nloc) != hipSuccess) {
+            (void)hipGetLastError();
+            fprintf(stderr, "shd_tcp_run: no device memory for the hosts' heartbeat intervals\n");
+            rc = -12;
+            goto done;
+        }
+        HCHECK(hipMemcpy(d_hbh, m->host_heartbeat + h0, sizeof(uint64_t) * (size_t)nloc, hipMemcpyHostToDevice));
+        g.hb_host = d_hbh;
     }
     if (any_pcap) {   // a ring per capture host of this engine, by capture slot: nothing per model host but the slot
         std::vector<int32_t> slot(nloc, -1);

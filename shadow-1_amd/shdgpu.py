@@ -206,7 +206,8 @@ class TcpModel(C.Structure):
                 ("proc_app", P(C.c_int32)), ("app_spec", P(C.c_uint32)), ("n_app_specs", C.c_int32),
                 ("udp_payload", C.c_uint32), ("app_peer", P(C.c_int32)), ("dest_cum", P(C.c_double)),
                 ("host_class", P(C.c_uint8)), ("n_classes", C.c_int32), ("_pad2", C.c_int32),
-                ("pcap_host", P(C.c_uint8)), ("pcap_ring", C.c_uint32), ("_pad10", C.c_uint32)]
+                ("pcap_host", P(C.c_uint8)), ("pcap_ring", C.c_uint32), ("_pad10", C.c_uint32),
+                ("bootstrap_end", C.c_uint64), ("host_heartbeat", P(C.c_uint64))]
 
 
 class TcpResult(C.Structure):
@@ -418,9 +419,10 @@ class GraphArrays:
         return len(self.src)
 
 
-def load_config(xml: bytes):
+def load_config(xml: bytes, with_bootstrap: bool = False):
     """shadow.config.xml -> (hosts: list of dicts in registration order,
-    ips: host-order uint32 array from shd_dns_assign, stop_time_s, topology text or path)."""
+    ips: host-order uint32 array from shd_dns_assign, stop_time_s, topology text or path);
+    with_bootstrap: then also <shadow bootstraptime> in seconds (0: none)."""
     ptr = P(Config)()
     check(lib().shd_config_load_buffer(xml, len(xml), C.byref(ptr)), "shd_config_load_buffer")
     try:
@@ -435,7 +437,8 @@ def load_config(xml: bytes):
         ips = np.zeros(max(c.n_hosts, 1), dtype=np.uint32)
         check(lib().shd_dns_assign(ptr, ips.ctypes.data_as(P(C.c_uint32))), "shd_dns_assign")
         topo = dec(c.topology_text) if c.topology_text else dec(c.topology_path)
-        return hosts, ips[:c.n_hosts], c.stop_time_s, topo
+        boot = (int(c.bootstrap_time_s),) if with_bootstrap else ()
+        return (hosts, ips[:c.n_hosts], c.stop_time_s, topo) + boot
     finally:
         lib().shd_config_free(ptr)
 

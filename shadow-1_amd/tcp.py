@@ -126,7 +126,11 @@ def run(model: S.ModelArrays, g: S.GraphArrays, ips, procs, peers, nbytes=20000,
     with or without trace.  The result then has pcap_records {host index:
     S.PCAP_DTYPE array in the interface's order} for the captured hosts the
     result covers, pcap_drains and pcap_ring_peak; S.write_pcap_files makes
-    the files."""
+    the files.
+    The model's bootstrap period (model.struct.bootstrap_end) and per-host
+    heartbeat intervals (model.host_heartbeat) run as the reference's loop runs
+    them (shd_tcp_model.bootstrap_end / host_heartbeat), on one engine and
+    with comm."""
     if mode == "device" and not guess_reversed and not g.directed:
         m = model.struct
         H = int(m.n_hosts)
@@ -168,11 +172,13 @@ def run(model: S.ModelArrays, g: S.GraphArrays, ips, procs, peers, nbytes=20000,
     raise S.ShdError("shd_tcp_run: the first-touch order did not settle in 8 runs")
 
 
-def _run_once(model, ips, procs, peers, lat, rel, hvi, nbytes, trace, recv_buf, send_buf, tcp_window,
-              packets_per_host, node=False, qdisc=0, pc=None, udp=None, comm=None, pcap=None):
-    """one shd_tcp_run on the given path tables, or with pc (sim.PathCache) on
-    the cache itself (hvi: graph vertices then); None when that run's
-    first-touch choices were contradicted (SHD_TCP_ERR_FIRST_TOUCH)"""
+def fill_model(model, ips, procs, peers, lat, rel, hvi, nbytes, recv_buf=RECV_BUF, send_buf=SEND_BUF,
+               tcp_window=TCP_WINDOW, packets_per_host=0, qdisc=0, pc=None, udp=None, pcap=None):
+    """The shd_tcp_model of one run (no device needed): (TcpModel, the arrays
+    its pointers refer to -- keep them alive as long as the struct is used).
+    The model's bootstrap period and per-host heartbeat intervals
+    (model.struct.bootstrap_end, model.host_heartbeat: <shadow bootstraptime>,
+    <host heartbeatfrequency>) go in as they are."""
     m = model.struct
     H = int(m.n_hosts)
     keep = dict(ip=np.ascontiguousarray(ips, dtype=np.uint32), hv=np.ascontiguousarray(hvi, dtype=np.int32),
@@ -197,6 +203,10 @@ def _run_once(model, ips, procs, peers, lat, rel, hvi, nbytes, trace, recv_buf, 
     tm.proc_peer = S.as_ptr(keep["pp"], C.c_int32)
     tm.end_time = m.end_time
     tm.heartbeat_interval = m.heartbeat_interval
+    tm.bootstrap_end = m.bootstrap_end
+    if model.host_heartbeat is not None:
+        keep["hb"] = np.ascontiguousarray(model.host_heartbeat, dtype=np.uint64)
+        tm.host_heartbeat = S.as_ptr(keep["hb"], C.c_uint64)
     tm.tcp_bytes = nbytes
     tm.recv_buf = recv_buf
     tm.send_buf = send_buf
@@ -222,6 +232,16 @@ def _run_once(model, ips, procs, peers, lat, rel, hvi, nbytes, trace, recv_buf, 
         keep["pc"][np.asarray(list(pcap["hosts"]), dtype=np.int64)] = 1
         tm.pcap_host = S.as_ptr(keep["pc"], C.c_uint8)
         tm.pcap_ring = int(pcap.get("ring", 0))
+    return tm, keep
+
+
+def _run_once(model, ips, procs, peers, lat, rel, hvi, nbytes, trace, recv_buf, send_buf, tcp_window,
+              packets_per_host, node=False, qdisc=0, pc=None, udp=None, comm=None, pcap=None):
+    """one shd_tcp_run on the given path tables, or with pc (sim.PathCache) on
+    the cache itself (hvi: graph vertices then); None when that run's
+    first-touch choices were contradicted (SHD_TCP_ERR_FIRST_TOUCH)"""
+    tm, keep = fill_model(model, ips, procs, peers, lat, rel, hvi, nbytes, recv_buf, send_buf, tcp_window,
+                          packets_per_host, qdisc, pc=pc, udp=udp, pcap=pcap)
     res = C.POINTER(S.TcpResult)()
     bits = (S.TCP_TRACE_STATUS if trace else 0) | (S.TCP_TRACE_NODE if node else 0)
     if comm is not None:
@@ -268,7 +288,9 @@ def _run_once(model, ips, procs, peers, lat, rel, hvi, nbytes, trace, recv_buf, 
             for i in range(HL):
                 c = np.ascontiguousarray(cnt[i, :int(nhb[i])])
                 lp = C.POINTER(S.Lines)()
-                S.check(S.lib().shd_tracker_node_lines(c.ctypes.data_as(C.POINTER(C.c_uint64)), len(c), hb, h0 + i,
+                # the host's own interval: the line's first field and the heartbeats' times
+                hbi = int(keep["hb"][h0 + i]) if "hb" in keep else hb
+                S.check(S.lib().shd_tracker_node_lines(c.ctypes.data_as(C.POINTER(C.c_uint64)), len(c), hbi, h0 + i,
                                                        C.byref(lp)), "shd_tracker_node_lines")
                 nl += S.take_lines(lp)
             out["node_lines"] = sorted(nl, key=lambda x: (x[0], x[1]))

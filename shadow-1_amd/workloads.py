@@ -295,9 +295,12 @@ def config_model(xml: bytes, *, load=16, payload=1, seed=1, trace=False, topolog
       topology_new on the inline or referenced graphml;
       topology_attach per host (hints, one RNG draw) with the vertex bandwidth
         unless the host sets its own (host.c:176-192);
-      process_schedule per process at boot (host.c:372-390): pushed starts.
+      process_schedule per process at boot (host.c:372-390): pushed starts;
+      <shadow bootstraptime> as the model's bootstrap_end and each host's
+        heartbeatfrequency as its heartbeat interval.
     Returns (graph, model, pushed start events, host names, ips)."""
-    hosts, ips, stop_s, topo = S.load_config(xml)
+    hosts, ips, stop_s, topo, boot_s = S.load_config(xml, with_bootstrap=True)
+    caps.setdefault("bootstrap_end", boot_s * S.SHD_SEC)
     if topology_bytes is not None:
         gxml = topology_bytes
     elif topo and topo.lstrip().startswith("<"):
