@@ -34,6 +34,56 @@ constexpr int kPool = 288;             // deferred sends of the wave between flu
                                        // per block: four blocks per CU once hosts fill the machine
 constexpr int kBlock = 64;             // round-kernel workgroup: one wave, one host per lane
 
+// Wave folds without LDS, for the persistent rounds (their share fold and the
+// gather's).  A row of 16 lanes folds in four DPP steps -- lane ^ 1, lane ^ 2
+// (quad permutes), then the mirrors of 8 and of 16 lanes, which pair each
+// already uniform group with its neighbour -- and the four rows' results are
+// read into scalar registers and folded there, so the value comes out
+// wave-uniform (no readfirstlane after it) and nothing waits on the LDS queue,
+// where a __shfl_xor ladder is six dependent ds_bpermute round trips per value.
+// The whole wave calls these (kBlock == 64, wave-uniform flow); a lane with
+// nothing to add passes the identity, which is also what a DPP read of a
+// disabled lane yields (`old` operand).
+constexpr int kDppXor1 = 0xB1, kDppXor2 = 0x4E, kDppHalfMirror = 0x141, kDppMirror = 0x140;
+template <int CTRL>
+__device__ __forceinline__ uint32_t dpp_u32(uint32_t ident, uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp((int)ident, (int)v, CTRL, 0xf, 0xf, false);
+}
+template <int CTRL>
+__device__ __forceinline__ uint64_t dpp_u64(uint64_t ident, uint64_t v) {
+    return ((uint64_t)dpp_u32<CTRL>((uint32_t)(ident >> 32), (uint32_t)(v >> 32)) << 32) |
+           dpp_u32<CTRL>((uint32_t)ident, (uint32_t)v);
+}
+__device__ __forceinline__ uint32_t lane_u32(uint32_t v, int lane) {
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, lane);
+}
+__device__ __forceinline__ uint64_t lane_u64(uint64_t v, int lane) {
+    return ((uint64_t)lane_u32((uint32_t)(v >> 32), lane) << 32) | lane_u32((uint32_t)v, lane);
+}
+struct FoldMin { template <class T> __device__ __forceinline__ T operator()(T a, T b) const { return b < a ? b : a; } };
+struct FoldSum { template <class T> __device__ __forceinline__ T operator()(T a, T b) const { return a + b; } };
+struct FoldOr { template <class T> __device__ __forceinline__ T operator()(T a, T b) const { return a | b; } };
+template <class Op>
+__device__ __forceinline__ uint32_t wave_fold_u32(uint32_t v, uint32_t ident, Op op) {
+    v = op(v, dpp_u32<kDppXor1>(ident, v));
+    v = op(v, dpp_u32<kDppXor2>(ident, v));
+    v = op(v, dpp_u32<kDppHalfMirror>(ident, v));
+    v = op(v, dpp_u32<kDppMirror>(ident, v));
+    return op(op(lane_u32(v, 0), lane_u32(v, 16)), op(lane_u32(v, 32), lane_u32(v, 48)));
+}
+template <class Op>
+__device__ __forceinline__ uint64_t wave_fold_u64(uint64_t v, uint64_t ident, Op op) {
+    v = op(v, dpp_u64<kDppXor1>(ident, v));
+    v = op(v, dpp_u64<kDppXor2>(ident, v));
+    v = op(v, dpp_u64<kDppHalfMirror>(ident, v));
+    v = op(v, dpp_u64<kDppMirror>(ident, v));
+    return op(op(lane_u64(v, 0), lane_u64(v, 16)), op(lane_u64(v, 32), lane_u64(v, 48)));
+}
+__device__ __forceinline__ uint64_t wave_min_u64(uint64_t v) { return wave_fold_u64(v, kInf, FoldMin{}); }
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) { return wave_fold_u32(v, 0u, FoldSum{}); }
+__device__ __forceinline__ uint32_t wave_or_u32(uint32_t v) { return wave_fold_u32(v, 0u, FoldOr{}); }
+__device__ __forceinline__ uint64_t wave_or_u64(uint64_t v) { return wave_fold_u64(v, 0ull, FoldOr{}); }
+
 struct CodelEnt {
     uint64_t ts;
     uint32_t src;

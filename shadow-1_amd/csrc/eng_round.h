@@ -89,6 +89,43 @@ __device__ __forceinline__ uint32_t bit_at(const uint32_t (&w)[kNBW], uint32_t p
     return (v >> (p & 31)) & 1u;
 }
 
+// The persistent rounds' bitmap work on the words that matter.  Every host's
+// window sits at the same ring positions (the round's first bin is the
+// wave's), so the few bits a round needs of a lane's 8-word bitmap are in two
+// words picked by a wave-uniform index:
+// the ring's 64 bits from position p on (at least 33 of them: the second
+// word's upper part is cut by the shift), bit j = ring position p + j
+__device__ __forceinline__ uint64_t bm_span(const uint32_t (&w)[kNBW], uint32_t p) {
+    static_assert(kNBW == 8, "eight words");
+    uint32_t lo, hi;
+    switch ((p >> 5) & (kNBW - 1)) {   // (uniform: a scalar branch)
+        case 0: lo = w[0]; hi = w[1]; break;
+        case 1: lo = w[1]; hi = w[2]; break;
+        case 2: lo = w[2]; hi = w[3]; break;
+        case 3: lo = w[3]; hi = w[4]; break;
+        case 4: lo = w[4]; hi = w[5]; break;
+        case 5: lo = w[5]; hi = w[6]; break;
+        case 6: lo = w[6]; hi = w[7]; break;
+        default: lo = w[7]; hi = w[0]; break;
+    }
+    return ((((uint64_t)hi) << 32) | lo) >> (p & 31u);
+}
+// the bits m (bit j: ring position p + j) cleared from a bitmap
+__device__ __forceinline__ void bm_clear(uint32_t (&w)[kNBW], uint32_t p, uint32_t m) {
+    const uint64_t mm = ~((uint64_t)m << (p & 31u));
+    const uint32_t lo = (uint32_t)mm, hi = (uint32_t)(mm >> 32);
+    switch ((p >> 5) & (kNBW - 1)) {
+        case 0: w[0] &= lo; w[1] &= hi; break;
+        case 1: w[1] &= lo; w[2] &= hi; break;
+        case 2: w[2] &= lo; w[3] &= hi; break;
+        case 3: w[3] &= lo; w[4] &= hi; break;
+        case 4: w[4] &= lo; w[5] &= hi; break;
+        case 5: w[5] &= lo; w[6] &= hi; break;
+        case 6: w[6] &= lo; w[7] &= hi; break;
+        default: w[7] &= lo; w[0] &= hi; break;
+    }
+}
+
 // the lane's host (P.nloc: none)
 __device__ __forceinline__ int32_t lane_host(const DParams& P) {
     return (int32_t)threadIdx.x < P.hpw ? (int32_t)blockIdx.x * P.hpw + (int32_t)threadIdx.x : P.nloc;
@@ -1025,6 +1062,7 @@ __device__ __forceinline__ void ps_prologue(const DParams& P, HostCtx& c, bool a
                                             uint32_t wbits, const SpIn* sp = nullptr) {
     const uint64_t b0 = ws >> P.bin_shift;
     const uint32_t nbin = P.bins ? (uint32_t)(((we - 1) >> P.bin_shift) - b0) + 1u : 0u;
+    uint32_t clr = 0;   // bit j: bin b0 + j is reset below, its bit cleared from w at the end
     // the window's bins, every slot of a non-empty one in one round trip
     EvV bx[3][kBinCap];
     if (active && P.bins) {
@@ -1088,25 +1126,24 @@ __device__ __forceinline__ void ps_prologue(const DParams& P, HostCtx& c, bool a
                                        __HIP_MEMORY_SCOPE_AGENT);
                     const uint32_t m = 1u << (p & 31);
                     atomicAnd(&P.bin_bits[(size_t)c.l * kNBW + (p >> 5)], ~m);
-#pragma unroll
-                    for (int k = 0; k < (int)kNBW; k++)
-                        if ((p >> 5) == (uint32_t)k) w[k] &= ~m;
+                    clr |= 1u << j;
                 }
             }
         }
     }
+    if (P.bins) bm_clear(w, (uint32_t)b0 & (kNB - 1), clr);
     TIMP(2);
 }
 
 // k_round_ps, a round whose window the previous round loaded ahead (every
 // host of the wave unnoted): the due list is in s_due already -- pnd sorted
 // events of the bins from the previous window's end on, of which those before
-// `we` are this round's -- and the bitmap of the previous round's close (pw)
-// names the window's non-empty bins.  The bins wholly consumed are reset as
-// in ps_prologue; their bits go to cm, cleared from the bitmap loaded at this
-// round's start once it has landed (ps_loop_close).
+// `we` are this round's -- and the span of the previous round's close bitmap
+// (pspan) names the window's non-empty bins.  The bins wholly consumed are reset as
+// in ps_prologue; their bits go to clr (bit j: bin b0 + j), cleared from the
+// bitmap loaded at this round's start once it has landed (ps_loop_close).
 __device__ __forceinline__ void ps_prologue_pf(const DParams& P, HostCtx& c, bool active, uint64_t ws, uint64_t we,
-                                               uint32_t pnd, uint32_t wbits, uint32_t (&cm)[kNBW]) {
+                                               uint32_t pnd, uint32_t wbits, uint32_t& clr) {
     const uint64_t b0 = ws >> P.bin_shift;
     const uint32_t nbin = (uint32_t)(((we - 1) >> P.bin_shift) - b0) + 1u;
     if (active) {
@@ -1123,9 +1160,7 @@ __device__ __forceinline__ void ps_prologue_pf(const DParams& P, HostCtx& c, boo
                 __hip_atomic_store(&P.bin_n[(size_t)c.l * kNB + p], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 const uint32_t m = 1u << (p & 31);
                 atomicAnd(&P.bin_bits[(size_t)c.l * kNBW + (p >> 5)], ~m);
-#pragma unroll
-                for (int k = 0; k < (int)kNBW; k++)
-                    if ((p >> 5) == (uint32_t)k) cm[k] |= m;
+                clr |= 1u << j;
             }
         }
     }
@@ -1138,14 +1173,14 @@ struct PfBins {
     EvV x[kPfBins][kBinCap];
     uint32_t m;   // bit j: bin b + j was loaded
 };
-__device__ __forceinline__ void pf_issue(const PsRsrc& R, uint32_t lb, uint64_t b, const uint32_t (&w)[kNBW],
-                                         bool has, PfBins& pb) {
+// (sp: the bitmap's span from bin b on, bm_span)
+__device__ __forceinline__ void pf_issue(const PsRsrc& R, uint32_t lb, uint64_t b, uint64_t sp, bool has, PfBins& pb) {
     pb.m = 0;
     if (!has) return;
 #pragma unroll
     for (uint32_t j = 0; j < kPfBins; j++) {
         const uint32_t p = (uint32_t)(b + j) & (kNB - 1);
-        if (!bit_at(w, p)) continue;
+        if (!((sp >> j) & 1ull)) continue;
         pb.m |= 1u << j;
         const uint32_t bi = lb * kNB + p;
 #pragma unroll
@@ -1180,41 +1215,44 @@ __device__ __forceinline__ uint32_t pf_stage(const PfBins& pb, uint64_t lo, uint
     return nw;
 }
 
-// the window bins of a bitmap (bit j: bin b0 + j is non-empty); an idle
-// host's next time from its own next event and its bitmap
-__device__ __forceinline__ uint32_t ps_window_bits(const DParams& P, HostCtx& c, const uint32_t (&w)[kNBW],
-                                                   uint64_t ws, uint64_t we) {
+// the window bins of a bitmap (bit j: bin b0 + j is non-empty), from its span
+// sp that starts d bins before the window's first (bm_span; d + 3 <= 33)
+__device__ __forceinline__ uint32_t ps_window_bits(const DParams& P, HostCtx& c, uint64_t sp, uint32_t d, uint64_t ws,
+                                                   uint64_t we) {
     const uint64_t b0 = ws >> P.bin_shift;
     const uint32_t nbin = P.bins ? (uint32_t)(((we - 1) >> P.bin_shift) - b0) + 1u : 0u;
-    uint32_t wbits = 0;
-    if (P.bins) {
-#pragma unroll
-        for (uint32_t j = 0; j < 3; j++)
-            if (j < nbin) wbits |= bit_at(w, (uint32_t)(b0 + j) & (kNB - 1)) << j;
-    }
     if (nbin > 3) c.err |= SHD_ERR_INTERNAL;
-    return wbits;
+    const uint32_t wmask = nbin >= 3 ? 7u : (1u << nbin) - 1u;   // (no calendar: none)
+    return (uint32_t)(sp >> d) & wmask;
 }
-__device__ __forceinline__ uint64_t ps_idle_next(const DParams& P, const uint32_t (&w)[kNBW], uint64_t t0,
-                                                 uint64_t we) {
-    uint64_t next = t0;
-    if (P.bins) {
-        const uint64_t cb = cal_lower_bound(P, w, we);
-        next = cb < next ? cb : next;
-    }
-    return next;
+__device__ __forceinline__ uint32_t ps_window_bits(const DParams& P, HostCtx& c, const uint32_t (&w)[kNBW],
+                                                   uint64_t ws, uint64_t we) {
+    const uint64_t sp = P.bins ? bm_span(w, (uint32_t)(ws >> P.bin_shift) & (kNB - 1)) : 0ull;
+    return ps_window_bits(P, c, sp, 0u, ws, we);
+}
+// cal_lower_bound with the bitmap's span from we's bin on at hand (HAVE; bm_span):
+// the span's first set bit is the bitmap's first from there on when it has
+// one (a host with a calendar event within 33 bins: nearly every one), and the
+// eight-word scan is left to the lanes whose span is empty
+template <bool HAVE>
+__device__ __forceinline__ uint64_t cal_lower_bound_sp(const DParams& P, const uint32_t (&w)[kNBW], uint64_t sp,
+                                                       uint64_t we) {
+    if (!HAVE || sp == 0) return cal_lower_bound(P, w, we);
+    const uint64_t t = ((we >> P.bin_shift) + (uint32_t)__builtin_ctzll(sp)) << P.bin_shift;
+    return t > we ? t : we;
 }
 
 // The round's event loop (as round_body's: per-lane state 0 needs its next
 // event, 1 runs one, 2 waits for a flush, 3 done; wave-uniform exits only)
 // and its close: the lane's next time (an idle lane's from its timers and
-// bitmap), the last flush's stores.  cm: bits to clear from w first (bins the
-// prologue reset, when w was loaded in parallel).  PF: the next window's bins
-// are loaded between the loop and the close, into *pb.
+// bitmap), the last flush's stores.  PF: clr (bit j: ring position clr_p + j)
+// is cleared from w first (bins the prologue reset, when w was loaded in
+// parallel), and the next window's bins are loaded between the loop and the
+// close, into *pb; *span: the bitmap's span from we's bin on, for the next round.
 template <bool PF>
 __device__ __forceinline__ void ps_loop_close(const DParams& P, HostCtx& c, bool active, bool has, const PsRsrc& R,
-                                              uint32_t lb, uint64_t we, uint32_t (&w)[kNBW],
-                                              const uint32_t (&cm)[kNBW], uint64_t& next, PfBins* pb) {
+                                              uint32_t lb, uint64_t we, uint32_t (&w)[kNBW], uint32_t clr_p,
+                                              uint32_t clr, uint64_t& next, PfBins* pb, uint64_t* span) {
     PendDel pd;
     pd.kind = 0;
 #ifdef SHD_TIMING_LIGHT
@@ -1318,18 +1356,27 @@ __device__ __forceinline__ void ps_loop_close(const DParams& P, HostCtx& c, bool
     TIMVP(15, t_q[1]);   //       begin_event
     TIMVP(19, t_q[2]);   //       the fused notification (the rest: the fused refill, the loop's own)
 #endif
-#pragma unroll
-    for (int k = 0; k < (int)kNBW; k++) w[k] &= ~cm[k];
-    if (PF) pf_issue(R, lb, we >> P.bin_shift, w, has, *pb);
+    uint64_t sp = 0;
+    if (PF) {
+        bm_clear(w, clr_p, clr);
+        const uint64_t b1 = we >> P.bin_shift;
+        sp = bm_span(w, (uint32_t)b1 & (kNB - 1));
+        *span = sp;
+        pf_issue(R, lb, b1, sp, has, *pb);
+    }
     if (active) {
         next = host_next(c);
         if (c.min_emit < next) next = c.min_emit;
         if (P.bins) {   // (the consumed bins were cleared in w)
-            const uint64_t cb = cal_lower_bound(P, w, we);
+            const uint64_t cb = cal_lower_bound_sp<PF>(P, w, sp, we);
             next = cb < next ? cb : next;
         }
     } else if (has) {
-        next = ps_idle_next(P, w, host_next(c), we);
+        next = host_next(c);
+        if (P.bins) {
+            const uint64_t cb = cal_lower_bound_sp<PF>(P, w, sp, we);
+            next = cb < next ? cb : next;
+        }
     }
     flush_finish(P, c, pd);
     TIMP(5);
@@ -1342,10 +1389,7 @@ __device__ __forceinline__ void ps_round_body(const DParams& P, HostCtx& c, bool
                                               uint32_t (&w)[kNBW], uint32_t wbits, uint64_t& next,
                                               const SpIn* sp = nullptr) {
     ps_prologue<SP>(P, c, active, lb, R, ws, we, parity, nin, w, wbits, sp);
-    uint32_t cm[kNBW];
-#pragma unroll
-    for (int k = 0; k < (int)kNBW; k++) cm[k] = 0;
-    ps_loop_close<false>(P, c, active, active, R, lb, we, w, cm, next, nullptr);
+    ps_loop_close<false>(P, c, active, active, R, lb, we, w, 0u, 0u, next, nullptr, nullptr);
 }
 
 // The shares' granules are stored in three planes (round 6): granule g of slot
@@ -1424,7 +1468,8 @@ __device__ __forceinline__ bool ps_gather(__amdgpu_buffer_rsrc_t rs, uint32_t ns
                 next = t < next ? t : next;
                 flags |= a[k].z;
                 nev += b[k].x; npkt += b[k].y; nact += b[k].z;
-                if (DIRTY) {
+                // (a share that names nothing -- nearly all do -- is three kDirtyNone: all bits set)
+                if (DIRTY && (d[k].x & d[k].y & d[k].z) != kDirtyNone) {
                     const uint32_t v[3] = {d[k].x, d[k].y, d[k].z};
 #pragma unroll
                     for (int q = 0; q < 3; q++) {
@@ -1438,21 +1483,17 @@ __device__ __forceinline__ bool ps_gather(__amdgpu_buffer_rsrc_t rs, uint32_t ns
             if (wall_clock64() - t0 > ticks) return false;
         }
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        const uint64_t o = __shfl_xor(next, off, 64);
-        next = o < next ? o : next;
-        flags |= __shfl_xor(flags, off, 64);
-        nev += __shfl_xor(nev, off, 64);
-        npkt += __shfl_xor(npkt, off, 64);
-        nact += __shfl_xor(nact, off, 64);
-        if (DIRTY) {
-            dm |= __shfl_xor(dm, off, 64);
-            da |= __shfl_xor(da, off, 64);
-        }
+    // the folds, wave-uniform (scalar registers); the counts only where they were loaded
+    next = wave_min_u64(next);
+    flags = wave_or_u32(flags);
+    if (counts) {
+        nev = wave_sum_u32(nev);
+        npkt = wave_sum_u32(npkt);
+        nact = wave_sum_u32(nact);
     }
     if (DIRTY) {
-        *dmask = dm;
-        *dall = da != 0;
+        *dmask = wave_or_u64(dm);
+        *dall = wave_or_u32(da) != 0;
     }
     return true;
 }
@@ -1556,14 +1597,13 @@ __global__ __launch_bounds__(kBlock) void k_round_ps(uint64_t window, int nb, De
     const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
     // the prefetch carried from a round to the next (wave-uniform but pnd,
     // dirty): valid, its first bin, the due events staged (kDueCap + 1:
-    // overflow), the bitmap of that round's close, named by a share
+    // overflow), the span from that bin on of that round's close bitmap
+    // (bm_span: the next window's bits), named by a share
     const bool pfm = kPsPf && P0.bins != nullptr;
     bool pf = false;
     uint64_t pf_b0 = 0;
     uint32_t pnd = 0, dirty = 0;
-    uint32_t pw[kNBW];
-#pragma unroll
-    for (int k = 0; k < (int)kNBW; k++) pw[k] = 0;
+    uint64_t pspan = 0;
     for (int i = 0; i < nb; i++) {
         PS_PARAMS(i);
         const unsigned long long t_start = wall_clock64();
@@ -1580,9 +1620,9 @@ __global__ __launch_bounds__(kBlock) void k_round_ps(uint64_t window, int nb, De
         const bool fast = pf && ((we - 1) >> P.bin_shift) <= pf_b0 + (kPfBins - 1) &&
                           __ballot(has && (dirty != 0 || pnd > (uint32_t)kDueCap)) == 0;
         ps_round_reset(P, c, ws, we, parity, pfm);
-        uint32_t w[kNBW], cm[kNBW];
+        uint32_t w[kNBW], clr = 0;
 #pragma unroll
-        for (int k = 0; k < (int)kNBW; k++) { w[k] = 0; cm[k] = 0; }
+        for (int k = 0; k < (int)kNBW; k++) w[k] = 0;
         bool active = false;
         if (fast) {
             // the bitmap for the close and the next prefetch goes out now and is
@@ -1591,10 +1631,10 @@ __global__ __launch_bounds__(kBlock) void k_round_ps(uint64_t window, int nb, De
                 const uint4 x = ld16_sc1(R.bits, lb * 32u), y = ld16_sc1(R.bits, lb * 32u + 16u);
                 w[0] = x.x; w[1] = x.y; w[2] = x.z; w[3] = x.w; w[4] = y.x; w[5] = y.y; w[6] = y.z; w[7] = y.w;
             }
-            const uint32_t wbits = ps_window_bits(P, c, pw, ws, we);
+            const uint32_t wbits = ps_window_bits(P, c, pspan, (uint32_t)((ws >> P.bin_shift) - pf_b0), ws, we);
             TIMP(1);
             active = has && !(host_next(c) >= we && wbits == 0);   // (no inbox: it would have been named)
-            ps_prologue_pf(P, c, active, ws, we, pnd, wbits, cm);
+            ps_prologue_pf(P, c, active, ws, we, pnd, wbits, clr);
         } else {
             // the round's hand-off words: this parity's inbox count, the calendar bitmap
             uint32_t nin = 0;
@@ -1612,20 +1652,18 @@ __global__ __launch_bounds__(kBlock) void k_round_ps(uint64_t window, int nb, De
         }
         uint64_t next = kInf;
         PfBins pb;
-        ps_loop_close<kPsPf>(P, c, active, has, R, lb, we, w, cm, next, &pb);
+        uint64_t span = 0;
+        ps_loop_close<kPsPf>(P, c, active, has, R, lb, we, w, (uint32_t)(ws >> P.bin_shift) & (kNB - 1), clr, next, &pb,
+                             &span);
         acc[0] += c.c_events; acc[1] += c.c_pkt; acc[2] += c.c_sent;
         acc[3] += c.c_idrop; acc[4] += c.c_cdrop; acc[5] += c.c_recv;
         uint32_t nev = c.c_events, npkt = c.c_pkt, err = c.err;
         const uint32_t pend = c.n_pend ? kPsPend : 0u;
         const uint32_t nact = (uint32_t)__popcll(__ballot(nev != 0));
-        uint32_t fl = err | pend;
-        for (int off = 32; off > 0; off >>= 1) {
-            const uint64_t o = __shfl_xor(next, off, 64);
-            next = o < next ? o : next;
-            nev += __shfl_xor(nev, off, 64);
-            npkt += __shfl_xor(npkt, off, 64);
-            fl |= __shfl_xor(fl, off, 64);
-        }
+        const uint32_t fl = wave_or_u32(err | pend);
+        next = wave_min_u64(next);
+        nev = wave_sum_u32(nev);
+        npkt = wave_sum_u32(npkt);
         const uint32_t tag = tag0 + (uint32_t)i;
         const uint32_t base = (uint32_t)(i & 1) * nblk;
         ps_publish(rs, 2 * nblk, base + blockIdx.x, next, fl, nev, npkt, nact, tag, ps_noted(pfm));
@@ -1634,8 +1672,7 @@ __global__ __launch_bounds__(kBlock) void k_round_ps(uint64_t window, int nb, De
             const uint64_t b1 = we >> P.bin_shift;
             pnd = pf_stage(pb, we, (b1 + kPfBins) << P.bin_shift);
             pf_b0 = b1;
-#pragma unroll
-            for (int k = 0; k < (int)kNBW; k++) pw[k] = w[k];
+            pspan = span;
         }
         uint64_t f_next, dm = 0;
         uint32_t f_fl, f_nev, f_npkt, f_nact;
@@ -1643,13 +1680,11 @@ __global__ __launch_bounds__(kBlock) void k_round_ps(uint64_t window, int nb, De
         const bool ok_v = ps_gather<kPsPf>(rs, 2 * nblk, base, nblk, tag, blockIdx.x == 0, ticks, f_next, f_fl, f_nev, f_npkt,
                                            f_nact, hb, (uint32_t)P.hpw, &dm, &dall);
         TIMP(7);
-        // the folds are wave-uniform: said so to the compiler, so that the
-        // round loop and the parity branch stay scalar (with a vector exit
-        // condition the host context would be merged through divergent flow)
+        // the folds come out of ps_gather in scalar registers, so the round
+        // loop and the parity branch stay scalar (with a vector exit condition
+        // the host context would be merged through divergent flow); the
+        // timeout is said to be wave-uniform here
         const bool ok = __builtin_amdgcn_readfirstlane((int)ok_v) != 0;
-        f_fl = __builtin_amdgcn_readfirstlane(f_fl);
-        f_next = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(f_next >> 32)) << 32) |
-                 (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)f_next);
         if (!ok) {   // a block never came: the launch is not resident (or a block faulted)
             if (threadIdx.x == 0) {
                 atomicOr(&ring[i + 1].error, SHD_ERR_INTERNAL);
@@ -1945,13 +1980,10 @@ __global__ __launch_bounds__(kBlock) void k_round_sp(uint64_t window, int nb, De
         // the active hosts, 64 at a time
         uint32_t nev = 0, npkt = 0, fl = 0, nhost = 0;
         sp_passes<true>(P, c, R, hb, nact, ws, we, parity, 0u, next, nev, npkt, fl, nhost, alist, lrec, lhn);
-        for (int off = 32; off > 0; off >>= 1) {
-            const uint64_t o = __shfl_xor(next, off, 64);
-            next = o < next ? o : next;
-            nev += __shfl_xor(nev, off, 64);
-            npkt += __shfl_xor(npkt, off, 64);
-            fl |= __shfl_xor(fl, off, 64);
-        }
+        next = wave_min_u64(next);
+        nev = wave_sum_u32(nev);
+        npkt = wave_sum_u32(npkt);
+        fl = wave_or_u32(fl);
         const uint32_t tag = tag0 + (uint32_t)i;
         const uint32_t sbase = (uint32_t)(i & 1) * nblk;
         ps_publish(rs, 2 * nblk, sbase + blockIdx.x, next, fl, nev, npkt, nhost, tag, ps_noted(false));
@@ -1961,10 +1993,7 @@ __global__ __launch_bounds__(kBlock) void k_round_sp(uint64_t window, int nb, De
         const bool ok_v = ps_gather<false, kSpGatherK>(rs, 2 * nblk, sbase, nblk, tag, blockIdx.x == 0, ticks, f_next, f_fl,
                                                        f_nev, f_npkt, f_nact);
         TIMP(7);
-        const bool ok = __builtin_amdgcn_readfirstlane((int)ok_v) != 0;
-        f_fl = __builtin_amdgcn_readfirstlane(f_fl);
-        f_next = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(f_next >> 32)) << 32) |
-                 (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)f_next);
+        const bool ok = __builtin_amdgcn_readfirstlane((int)ok_v) != 0;   // (the folds are scalar already)
         if (!ok) {
             if (lane == 0) {
                 atomicOr(&ring[i + 1].error, SHD_ERR_INTERNAL);

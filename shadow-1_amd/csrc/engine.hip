@@ -144,9 +144,14 @@ struct shd_eng {
     uint64_t round = 0;                     // rounds executed (parity = round & 1)
     // device-driven pipeline
     static constexpr int kBatch = 64;
-    static constexpr int kPsBatch = 128;      // rounds of a persistent launch (k_round_ps)
-    static constexpr int kRing = 2 * kBatch + 2;
-    static_assert(kPsBatch + 2 <= kRing, "a persistent batch's summaries fit the ring");
+    // rounds of a persistent launch (k_round_ps, k_round_sp).  A launch that
+    // halts or reaches the stop time leaves its loop, so a long batch wastes
+    // nothing, and every launch less is a seam less (the summaries' copy, the
+    // host's pass over them, the launch and the hosts' records reloaded):
+    // 1024 holds a simulated second of the C3 bench (997 rounds) in one launch
+    static constexpr int kPsBatch = 1024;
+    static constexpr int kRing = (kPsBatch > 2 * kBatch ? kPsBatch : 2 * kBatch) + 2;
+    static_assert(kPsBatch + 2 <= kRing && 2 * kBatch + 2 <= kRing, "a batch's summaries fit the ring");
     DevSummary* d_ring = nullptr;
     DevSummary* h_ring = nullptr;           // pinned
     uint32_t* d_halt = nullptr;
@@ -1428,7 +1433,10 @@ extern "C" int shd_eng_run_until(shd_eng* e, uint64_t t_stop, shd_run_stats* st)
         // batches when many are (C4: 14 %, 146 against 211 us; C3 at 100 k: 37 %,
         // 43 against 63 us).  Both are exact: the choice follows the last batch.
         const bool ps = tl && (e->ps_ok || (e->sp_ok && !e->sp_dense)) && !no_ps;
-        const int nb = ps ? shd_eng::kPsBatch : B;
+        // (SHD_PS_BATCH: a shorter persistent batch, for measurements)
+        static const int ps_nb = std::min(std::max((int)env_or("SHD_PS_BATCH", shd_eng::kPsBatch), 1),
+                                          (int)shd_eng::kPsBatch);
+        const int nb = ps ? ps_nb : B;
         if (ps) {
             if ((rc = launch_batch_ps(e, nb))) break;
             s.n_batches_persistent++;
