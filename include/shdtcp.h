@@ -15,6 +15,21 @@
  * reference's loop runs them (shd_tcp_model.bootstrap_end / host_heartbeat;
  * tests/test_tcp_options_gpu.py against tests/golden/ref_tcp_options.json).
  *
+ * A host's shape comes from the model.  Its socket slots are the sockets it
+ * can ever create -- a socket is not released in a TCP run: for each of its
+ * server processes the listener and one child per client process that names
+ * it as its peer, one per client process of its own, and 16 for a datagram
+ * process (its own socket and the per-datagram sockets waiting at the
+ * interface); a host without processes has none.  The slots, the processes of
+ * a host and its interface's queue of sockets wanting to send are ranges of
+ * engine-wide arrays, so one hub host may serve dozens of clients beside
+ * thousands of single-client hosts that hold one slot each
+ * (shd_tcp_result.max_host_sockets / max_host_procs / sock_bytes;
+ * tests/test_tcp_hub_gpu.py against tests/golden/ref_tcp_hub.json).  What
+ * stays fixed is a listener's pending and child lists of 8: a server named
+ * by more than eight clients whose connections are all open before it accepts
+ * one ends the run with SHD_TCP_ERR_SOCKETS.
+ *
  * The boundary is the same one shdgpu.h draws for the UDP path: plain
  * pointers and sizes, no torch types.  Path latency and reliability per host
  * pair come either from libshdgpu's path cache itself (path_cache set: the
@@ -82,8 +97,9 @@ typedef struct shd_tcp_model {
      * every process runs the echo.  udp_payload: bytes per datagram (1 ..
      * 65507); app_peer [H]: the SHD_DEST_PEER host of each host; dest_cum
      * [n_classes][H] / host_class [H]: SHD_DEST_WEIGHTED's cumulative weights
-     * (host_class NULL: row 0).  A host then holds up to 16 sockets at once
-     * (8 otherwise): more set SHD_TCP_ERR_SOCKETS. */
+     * (host_class NULL: row 0).  A datagram process adds 16 socket slots to
+     * its host (the file comment's rule): more per-datagram sockets waiting
+     * at the interface at once set SHD_TCP_ERR_SOCKETS. */
     const int32_t* proc_app;
     const uint32_t* app_spec;
     int32_t n_app_specs;
@@ -227,13 +243,26 @@ typedef struct shd_tcp_result {
     uint64_t* pcap_off;               /* [n_local_hosts + 1] */
     uint64_t pcap_drains;
     uint32_t pcap_ring_peak, _pad11;
+    /* the shape the model gave this result's hosts (the file comment's rule):
+     * the most socket slots one of them used and the most processes one of
+     * them runs; sock_bytes: device bytes of this engine's socket slots,
+     * SHD_TCP_SOCK_BYTES for each slot of the rule's sum over its hosts */
+    uint32_t max_host_sockets;
+    uint32_t max_host_procs;
+    uint64_t sock_bytes;
 } shd_tcp_result;
+
+/* device bytes of one socket slot (its buffers, queues, SACK and retransmit
+ * state at their fixed capacities) */
+#define SHD_TCP_SOCK_BYTES 141888
 
 /* shd_tcp_run's `trace` bits */
 enum { SHD_TCP_TRACE_STATUS = 1, SHD_TCP_TRACE_NODE = 2 };
 
 enum {
-    SHD_TCP_ERR_EVQ = 1, SHD_TCP_ERR_POOL = 2, SHD_TCP_ERR_QUEUE = 4, SHD_TCP_ERR_SOCKETS = 8,
+    SHD_TCP_ERR_EVQ = 1, SHD_TCP_ERR_POOL = 2, SHD_TCP_ERR_QUEUE = 4,
+    SHD_TCP_ERR_SOCKETS = 8,   /* a host created more sockets than its slots (a datagram process with more
+                                  than 16 sockets at once), or a listener held more than 8 children */
     SHD_TCP_ERR_MAILBOX = 16, SHD_TCP_ERR_TRACE = 32, SHD_TCP_ERR_SACK = 64, SHD_TCP_ERR_INTERNAL = 128,
     SHD_TCP_ERR_QLOG = 256, SHD_TCP_ERR_FIRST_TOUCH = 512,
     SHD_TCP_ERR_PCAP = 1024   /* a capture ring filled between two drains (pcap_ring) */

@@ -27,7 +27,11 @@
 // another host goes into the round's mailbox with its packet copy and is
 // taken by the receiver's lane at the start of the next round.  Every piece
 // of state lives in HBM in fixed-capacity per-host / per-socket arrays; an
-// overflow sets an error bit instead of corrupting anything.
+// overflow sets an error bit instead of corrupting anything.  How many
+// sockets and processes a host has comes from the model (tcp_host_slots):
+// its socket slots, their directory (DKey) and its interface's queue are
+// ranges of engine-wide arrays, so a hub host with dozens of sockets runs
+// beside hosts that hold one.
 //
 // The work is branchy per-host control flow with a few events per host and
 // round: latency-bound by design ("TCP"); it shares nothing with
@@ -41,11 +45,13 @@
 
 #include <algorithm>
 #include <chrono>
+#include <map>
 #include <mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/shdtcp.h"
+#include "ght_order.h"    // GLib's hash-table order, for the lines of a retransmit queue's clear
 #include "shd_device.h"   // struct shd_pc: the path cache's device tables (shd_tcp_model.path_cache)
 // comm.hip: device buffers of per-peer sizes -- peer p gets send_bytes[p] from d_send +
 // send_off[p], this rank recv_bytes[p] from peer p into d_recv + recv_off[p] (the sizes
@@ -66,10 +72,9 @@ constexpr uint32_t kMTU = 1500, kHdr = 66, kMSS = kMTU - kHdr;
 constexpr uint32_t kHdrUdp = 42;    // CONFIG_HEADER_SIZE_UDPIPETH (definitions.h:176)
 constexpr uint16_t kUdpPort = 8998; // the datagram applications' port (test_phold.c's PHOLD_LISTEN_PORT)
 constexpr uint32_t kDgramMax = 65507;   // CONFIG_DATAGRAM_MAX_SIZE (definitions.h:193)
-constexpr int kSock = 8;            // sockets per host (a listener, its children, clients); a model with
-                                    // datagram processes gets 2 * kSock (their per-datagram sockets wait at the
-                                    // interface): Glob::spk, never more than the qdisc queues hold
-constexpr int kProcs = 8;           // processes per host
+constexpr int kUdpSlots = 16;       // socket slots a datagram process adds to its host (its own socket and the
+                                    // per-datagram sockets waiting at the interface); every other slot of a
+                                    // host comes from the model's processes (tcp_host_slots)
 constexpr uint32_t kQ = 4096;       // per-socket packet queues
 constexpr uint32_t kQc = 256;       // control-packet queue
 constexpr uint32_t kTimers = 256;   // pending RTO timer expirations
@@ -100,6 +105,8 @@ constexpr uint32_t kTrk = 10;       // tracker counters per direction (DHost::tr
 constexpr uint32_t kXRetx = 1;      // DPkt::xflags: the packet was retransmitted (PDS_SND_TCP_RETRANSMITTED)
 constexpr uint32_t kXUdp = 2;       // DPkt::xflags: a datagram (PUDP, packet.c:320-321)
 constexpr uint32_t kTrUdp = 1u << 31;   // TRec::flags: the record is a datagram's (packet_toString's PUDP form)
+constexpr uint32_t kTrIter = 1u << 30;  // TRec::flags: a retransmit-queue removal through the table's iterator
+                                        // (tcp_clear_retransmit; the host orders those lines: ght_order.h)
 constexpr uint32_t kLocalRanks = 6;  // path_cache mode: rows a lane can run in one round (more: fall back)
 constexpr int32_t kLocalRank0 = 0x7FFF0000;   // pseudo-ranks of a lane's in-round rows: past every real rank
 enum : uint32_t { kFtRowA = 0, kFtRowB = 1, kFtSelf = 2 };
@@ -166,7 +173,6 @@ template <uint32_t N> struct Ring {   // GQueue
     uint32_t head, n;
     int32_t a[N];
 };
-template <uint32_t N> struct IHeap { uint32_t n; int32_t a[N]; };   // priority_queue.c over indices
 // the same heap over packets ordered by TCP sequence, each entry carrying its
 // key ((seq << 32) | pool index): a level is one load, not an index then the
 // packet's sequence (a packet's sequence does not change while it is queued)
@@ -175,6 +181,22 @@ template <uint32_t N> struct THeap { uint32_t n; uint64_t a[N]; };  // timer exp
 struct Rng64 { int64_t a, b; };
 struct RVec { uint32_t n; Rng64 r[kRanges]; };
 struct Tally { int64_t last_ack; uint64_t ndup; RVec marked, sacked, retx, lost, tmp; };
+
+// A socket slot's entry in its host's directory (Glob::dir): what the
+// interface's association table is keyed by (network_interface.c:279-301,
+// 385-403) and whether the slot is taken, in one 16-byte word next to its
+// neighbours', so that a walk over a host's sockets is one load per slot
+// over contiguous memory instead of one line per 139-KB record.  Written by
+// dir_put wherever a socket's key fields change; the record stays the truth.
+enum : uint32_t { kDUsed = 1, kDAssoc = 2, kDGeneral = 4, kDUdp = 8 };
+struct alignas(16) DKey {
+    uint32_t ports;     // bound_port | peer_port << 16
+    uint32_t peer_ip;
+    uint32_t flags;     // kDUsed | kDAssoc | kDGeneral | kDUdp
+    uint32_t _pad;
+};
+static_assert(sizeof(DKey) == 16, "one 16-byte load per slot");
+constexpr uint32_t kDirPad = 4;     // entries past the last host's range (a walk loads four slots at a time)
 
 struct DSock {   // every scalar first (a few lines per socket), then the containers
     int16_t used, udp;      // udp: a datagram socket (udp.c), else TCP (the scalars' layout as before it)
@@ -218,6 +240,7 @@ struct DSock {   // every scalar first (a few lines per socket), then the contai
     int32_t sacks[kSacks];
     int32_t rtx[kQ]; uint32_t rtxs[kQ];
 };
+static_assert(sizeof(DSock) == SHD_TCP_SOCK_BYTES, "shdtcp.h states a socket slot's device bytes");
 struct DProc {
     int32_t host, index, peer, running, step, fd, listenfd, wait_fd;
     int32_t app, _pad;   // >= 0: the datagram application app_spec[4 * app ..] (else the TCP echo)
@@ -232,8 +255,11 @@ struct DHost {
     uint64_t rx_rem, rx_cap, rx_refill, tx_rem, tx_cap, tx_refill;
     uint64_t bw_down, bw_up;   // configured KiB/s (worker_getNodeBandwidth{Down,Up})
     int32_t refill_pending, nsock, next_handle;
-    IHeap<2 * kSock> fifo;
-    Ring<2 * kSock> rrq;    // the RR qdisc's sockets wanting to send (rrQueue, network_interface.c:58)
+    // the interface's sockets wanting to send, in the host's range of Glob::ifq
+    // (as many entries as it has socket slots): the FIFO qdisc's heap of
+    // ifq_n entries, or the RR qdisc's ring (rrQueue, network_interface.c:58)
+    // of ifq_n entries from ifq_head -- a run has one qdisc
+    uint32_t ifq_n, ifq_head;
     // CoDel (router_queue_codel.c)
     uint32_t cq_head, cq_n; uint64_t cq_total, cq_iexp, cq_next_drop; uint32_t cq_dc, cq_dc_last; int32_t cq_mode;
     uint32_t nfree, ntr, ntrs, nev;
@@ -271,9 +297,13 @@ struct Glob {
     uint64_t end_time, hb, W, now_dummy;
     uint32_t tcp_bytes, trace, recv_buf, send_buf, tcp_window, _pad;
     DHost* host;
-    DSock* sock;            // [H][spk]
+    DSock* sock;            // [sock_off[nloc]] host h's slots: [sock_off[h], sock_off[h + 1])
+    const int32_t* sock_off;   // [nloc + 1]
+    DKey* dir;              // [sock_off[nloc] + kDirPad] each slot's directory entry
+    int32_t* ifq;           // [sock_off[nloc]] each host's interface queue (DHost::ifq_n)
     DProc* proc;            // [P]
-    int32_t* host_procs;    // [H][kProcs]
+    const int32_t* proc_off;   // [nloc + 1] host h's processes: host_procs[proc_off[h] .. proc_off[h + 1])
+    const int32_t* host_procs;
     DPkt* pool;             // [H][pool_cap]
     int32_t* psack;         // [H][pool_cap][kPktSack] each pool slot's SACK list
     int32_t* freel;         // [H][pool_cap]
@@ -335,7 +365,6 @@ struct Glob {
     const double* dest_cum;
     const uint8_t* host_class;
     int32_t n_classes; uint32_t udp_payload;
-    int32_t spk, _pad7;     // sockets per host
     // a run sharded over a group (shd_tcp_run_group): this engine's hosts
     // [h0, h0 + nloc) of the model's H (the per-host arrays hold these; one
     // engine: h0 = 0, nloc = H), every host's address and bandwidths, each
@@ -389,13 +418,28 @@ struct L {
     // round so far (vertex * 2 + kind), in order: its pseudo-ranks
     uint32_t nlr;
     int32_t lr[kLocalRanks];
+    int32_t s0, scap;       // the host's socket slots: Glob::sock / dir / ifq [s0, s0 + scap)
 };
 __device__ __forceinline__ DPkt* PK(const L& c, int32_t i) { return &c.g->pool[(size_t)c.h * c.g->pool_cap + i]; }
 __device__ __forceinline__ int32_t* PSK(const L& c, int32_t i) {
     return c.g->psack + ((size_t)c.h * c.g->pool_cap + i) * kPktSack;
 }
 __device__ __forceinline__ int32_t sidx(const L& c, const DSock* k) { return (int32_t)(k - c.g->sock); }
-__device__ __forceinline__ DSock* SK(const L& c, int32_t j) { return &c.g->sock[(size_t)c.h * c.g->spk + j]; }
+__device__ __forceinline__ DSock* SK(const L& c, int32_t j) { return &c.g->sock[(size_t)c.s0 + j]; }
+__device__ __forceinline__ void lane_slots(L& c) {
+    c.s0 = c.g->sock_off[c.h];
+    c.scap = c.g->sock_off[c.h + 1] - c.s0;
+}
+// the slot's directory entry from its record
+__device__ void dir_put(const L& c, const DSock* k) {
+    DKey d;
+    d.ports = (uint32_t)k->bound_port | ((uint32_t)k->peer_port << 16);
+    d.peer_ip = k->peer_ip;
+    d.flags = (k->used ? kDUsed : 0u) | (k->assoc ? kDAssoc : 0u) | (k->assoc_general ? kDGeneral : 0u) |
+              (k->udp ? kDUdp : 0u);
+    d._pad = 0;
+    c.g->dir[sidx(c, k)] = d;
+}
 // packet_getHeaderSize (packet.c:318-323)
 __device__ __forceinline__ uint32_t hdr_of(const DPkt* p) { return (p->xflags & kXUdp) ? kHdrUdp : kHdr; }
 
@@ -425,44 +469,38 @@ __device__ uint32_t lcg_jump(uint32_t x, uint64_t n) {
 __device__ double next_double(uint32_t* s) { return (double)(((double)rand_r_dev(s)) / ((double)2147483647)); }
 
 // ------------------------------------------------------------ heaps (priority_queue.c)
-template <uint32_t N, class Less> __device__ uint32_t ih_up(IHeap<N>& q, uint32_t i, Less lt) {
-    while (i > 0 && lt(q.a[i], q.a[(i - 1) / 2])) { int32_t t = q.a[i]; q.a[i] = q.a[(i - 1) / 2]; q.a[(i - 1) / 2] = t; i = (i - 1) / 2; }
+// (the interface's heap of socket indices: a host's range of Glob::ifq, n entries of cap)
+template <class Less> __device__ uint32_t ih_up(int32_t* a, uint32_t i, Less lt) {
+    while (i > 0 && lt(a[i], a[(i - 1) / 2])) { int32_t t = a[i]; a[i] = a[(i - 1) / 2]; a[(i - 1) / 2] = t; i = (i - 1) / 2; }
     return i;
 }
-template <uint32_t N, class Less> __device__ uint32_t ih_down(IHeap<N>& q, uint32_t i, Less lt) {
+template <class Less> __device__ uint32_t ih_down(int32_t* a, uint32_t n, uint32_t i, Less lt) {
     uint32_t ch;
-    while ((ch = 2 * i + 1) < q.n) {
-        if (ch + 1 < q.n && lt(q.a[ch + 1], q.a[ch])) ch = ch + 1;
-        if (lt(q.a[ch], q.a[i])) { int32_t t = q.a[i]; q.a[i] = q.a[ch]; q.a[ch] = t; i = ch; } else break;
+    while ((ch = 2 * i + 1) < n) {
+        if (ch + 1 < n && lt(a[ch + 1], a[ch])) ch = ch + 1;
+        if (lt(a[ch], a[i])) { int32_t t = a[i]; a[i] = a[ch]; a[ch] = t; i = ch; } else break;
     }
     return i;
 }
-template <uint32_t N> __device__ int ih_find(const IHeap<N>& q, int32_t x) {
-    for (uint32_t i = 0; i < q.n; i++) if (q.a[i] == x) return (int)i;
+__device__ int ih_find(const int32_t* a, uint32_t n, int32_t x) {
+    for (uint32_t i = 0; i < n; i++) if (a[i] == x) return (int)i;
     return -1;
 }
-template <uint32_t N, class Less> __device__ bool ih_push(IHeap<N>& q, int32_t x, Less lt, uint32_t& err) {
-    const int old = ih_find(q, x);
-    if (old >= 0) { ih_up(q, ih_down(q, (uint32_t)old, lt), lt); return false; }
-    if (q.n >= N) { err |= SHD_TCP_ERR_QUEUE; return false; }
-    q.a[q.n++] = x;
-    ih_up(q, q.n - 1, lt);
+template <class Less> __device__ bool ih_push(int32_t* a, uint32_t& n, uint32_t cap, int32_t x, Less lt, uint32_t& err) {
+    const int old = ih_find(a, n, x);
+    if (old >= 0) { ih_up(a, ih_down(a, n, (uint32_t)old, lt), lt); return false; }
+    if (n >= cap) { err |= SHD_TCP_ERR_QUEUE; return false; }
+    a[n++] = x;
+    ih_up(a, n - 1, lt);
     return true;
 }
-// push of an element known to be absent (its membership is tracked outside)
-template <uint32_t N, class Less> __device__ bool ih_push_new(IHeap<N>& q, int32_t x, Less lt, uint32_t& err) {
-    if (q.n >= N) { err |= SHD_TCP_ERR_QUEUE; return false; }
-    q.a[q.n++] = x;
-    ih_up(q, q.n - 1, lt);
-    return true;
-}
-template <uint32_t N, class Less> __device__ int32_t ih_pop(IHeap<N>& q, Less lt) {
-    if (!q.n) return -1;
-    const int32_t x = q.a[0];
-    q.a[0] = q.a[q.n - 1];
-    q.a[q.n - 1] = x;
-    q.n--;
-    ih_down(q, 0, lt);
+template <class Less> __device__ int32_t ih_pop(int32_t* a, uint32_t& n, Less lt) {
+    if (!n) return -1;
+    const int32_t x = a[0];
+    a[0] = a[n - 1];
+    a[n - 1] = x;
+    n--;
+    ih_down(a, n, 0, lt);
     return x;
 }
 // packet_compareTCPSequence (packet.c:207-221) on the entries' keys; the
@@ -528,6 +566,24 @@ template <uint32_t N> __device__ int32_t rg_pop(Ring<N>& r) {
     r.n--;
     return x;
 }
+// the RR qdisc's ring over the host's range of Glob::ifq: its modulus is the
+// host's slot count (head < cap and n <= cap: one conditional subtraction)
+__device__ __forceinline__ uint32_t iq_at(const L& c, uint32_t i) {
+    const uint32_t j = c.H->ifq_head + i;
+    return j >= (uint32_t)c.scap ? j - (uint32_t)c.scap : j;
+}
+__device__ void iq_push(L& c, int32_t x) {
+    if (c.H->ifq_n >= (uint32_t)c.scap) { c.H->err |= SHD_TCP_ERR_QUEUE; return; }
+    c.g->ifq[c.s0 + iq_at(c, c.H->ifq_n)] = x;
+    c.H->ifq_n++;
+}
+__device__ int32_t iq_pop(L& c) {
+    if (!c.H->ifq_n) return -1;
+    const int32_t x = c.g->ifq[c.s0 + c.H->ifq_head];
+    c.H->ifq_head = iq_at(c, 1);
+    c.H->ifq_n--;
+    return x;
+}
 
 // ------------------------------------------------------------ event heap (event.c:110-153)
 __device__ __forceinline__ bool ev_less(const DEv& a, const DEv& b) {
@@ -580,7 +636,7 @@ __device__ bool sched_task(L& c, uint64_t delay, uint32_t kind, int32_t obj) {
 }
 
 // ------------------------------------------------------------ packets and their lines
-__device__ void pkt_status(L& c, int32_t pi, uint8_t st) {   // packet_addDeliveryStatus (packet.c:647-659)
+__device__ void pkt_status(L& c, int32_t pi, uint8_t st, uint32_t trflags = 0) {   // packet_addDeliveryStatus (packet.c:647-659)
     DPkt* p = PK(c, pi);
     DHost* H = c.H;
     if (st == S_SND_TCP_RETRANSMITTED) p->xflags |= kXRetx;   // packet_getDeliveryStatus's OR of every status
@@ -590,7 +646,7 @@ __device__ void pkt_status(L& c, int32_t pi, uint8_t st) {   // packet_addDelive
     if (H->ntr >= kTr) { H->err |= SHD_TCP_ERR_TRACE; return; }
     TRec* r = &c.g->tr[(size_t)c.h * kTr + H->ntr++];
     r->time = c.now; r->host = c.active; r->status = st;
-    r->host_id = p->host_id; r->pid = p->pid; r->flags = p->flags | ((p->xflags & kXUdp) ? kTrUdp : 0u);
+    r->host_id = p->host_id; r->pid = p->pid; r->flags = p->flags | ((p->xflags & kXUdp) ? kTrUdp : 0u) | trflags;
     r->sip = p->sip; r->dip = p->dip;
     r->sport = p->sport; r->dport = p->dport; r->seq = p->seq; r->ack = p->ack; r->win = p->win; r->len = p->len;
     r->tsval = p->tsval; r->tsecho = p->tsecho; r->nst = p->nst;
@@ -726,11 +782,10 @@ __device__ bool sock_add_output(L& c, DSock* k, int32_t pi) {   // socket.c:385-
     // networkinterface_wantsSend (network_interface.c:581-605): tracked once
     if (c.g->qdisc_rr) {
         bool found = false;   // g_queue_find
-        for (uint32_t i = 0; i < c.H->rrq.n; i++)
-            found |= c.H->rrq.a[(c.H->rrq.head + i) % (2 * kSock)] == sidx(c, k);
-        if (!found) rg_push(c.H->rrq, sidx(c, k), c.H->err);
-    } else if (ih_find(c.H->fifo, sidx(c, k)) < 0) {
-        ih_push(c.H->fifo, sidx(c, k), SockLess{&c}, c.H->err);
+        for (uint32_t i = 0; i < c.H->ifq_n; i++) found |= c.g->ifq[c.s0 + iq_at(c, i)] == sidx(c, k);
+        if (!found) iq_push(c, sidx(c, k));
+    } else if (ih_find(c.g->ifq + c.s0, c.H->ifq_n, sidx(c, k)) < 0) {
+        ih_push(c.g->ifq + c.s0, c.H->ifq_n, (uint32_t)c.scap, sidx(c, k), SockLess{&c}, c.H->err);
     }
     if_send_packets(c);
     return true;
@@ -941,11 +996,14 @@ __device__ void tcp_add_retransmit(L& c, DSock* k, int32_t pi) {   // tcp.c:854-
     k->rtx_len += p->len;
     if (space_out(k) == 0) sock_status(c, k, DS_WRITABLE, false);
 }
-__device__ void tcp_clear_retransmit(L& c, DSock* k, uint32_t seq) {   // tcp.c:876-897 (sequence order)
-    while (k->nrtx && k->rtxs[k->rh] < seq) {   // the lowest sequence below `seq` first
+// tcp.c:876-897.  The reference walks its GHashTable; here the lowest sequence
+// below `seq` goes first, and the lines say so (kTrIter): the host puts each
+// such run of lines into the table's order (order_iter_clears)
+__device__ void tcp_clear_retransmit(L& c, DSock* k, uint32_t seq) {
+    while (k->nrtx && k->rtxs[k->rh] < seq) {
         const int32_t pi = rtx_at(k, 0);
         k->rtx_len -= PK(c, pi)->len;
-        pkt_status(c, pi, S_SND_TCP_DEQUEUE_RETRANSMIT);
+        pkt_status(c, pi, S_SND_TCP_DEQUEUE_RETRANSMIT, kTrIter);
         rtx_remove_at(k, 0);
         pkt_unref(c, pi);
     }
@@ -1119,10 +1177,18 @@ __device__ void reno_timeout(DSock* k) {
 // ------------------------------------------------------------ TCP
 __device__ int32_t sock_new(L& c) {   // host_createDescriptor + tcp_new (tcp.c:2452-2512)
     DHost* H = c.H;
-    int32_t j = 0;   // a released datagram socket's slot first (udp_release)
-    while (j < H->nsock && SK(c, j)->used) j++;
+    // a released datagram socket's slot first (udp_release): the first slot the
+    // directory does not mark used
+    const DKey* d = c.g->dir + c.s0;
+    int32_t j = H->nsock;
+    for (int32_t b = 0; b < H->nsock && j == H->nsock; b += 4) {
+        const uint32_t f[4] = {d[b].flags, d[b + 1].flags, d[b + 2].flags, d[b + 3].flags};
+#pragma unroll
+        for (int32_t i = 3; i >= 0; i--)
+            if (b + i < H->nsock && !(f[i] & kDUsed)) j = b + i;
+    }
     if (j == H->nsock) {
-        if (H->nsock >= c.g->spk) { H->err |= SHD_TCP_ERR_SOCKETS; return -1; }
+        if (H->nsock >= c.scap) { H->err |= SHD_TCP_ERR_SOCKETS; return -1; }
         H->nsock++;
     }
     DSock* k = SK(c, j);
@@ -1131,6 +1197,7 @@ __device__ int32_t sock_new(L& c) {   // host_createDescriptor + tcp_new (tcp.c:
     k->used = 1; k->host = c.h; k->proc = -1; k->parent = -1; k->partial = -1;
     k->in.head = k->in.n = 0; k->out.head = k->out.n = 0; k->outctl.head = k->outctl.n = 0;
     k->state = TS_CLOSED; k->state_last = 0; k->flags = 0; k->error = 0;
+    dir_put(c, k);
     return si;
 }
 __device__ void sock_init_tcp(DSock* k, uint32_t recv_buf, uint32_t send_buf, uint32_t iw) {
@@ -1399,10 +1466,11 @@ __device__ void tcp_set_state(L& c, DSock* k, int st) {   // tcp.c:607-693
                 DSock* pa = &c.g->sock[k->parent];
                 for (uint32_t i = 0; i < pa->nkids; i++)
                     if (pa->kids[i] == sidx(c, k)) { pa->kids[i] = pa->kids[--pa->nkids]; break; }
-                if (pa->state == TS_CLOSED && pa->nkids == 0) { pa->assoc = 0; pa->assoc_general = 0; }
+                if (pa->state == TS_CLOSED && pa->nkids == 0) { pa->assoc = 0; pa->assoc_general = 0; dir_put(c, pa); }
             }
             k->assoc = 0;   // host_closeDescriptor: _host_disassociateInterface
             k->assoc_general = 0;
+            dir_put(c, k);
         }
     } else if (st == TS_TIMEWAIT) {
         const uint64_t delay = (k->child && k->parent >= 0) ? kSec : 60 * kSec;   // CONFIG_TCPCLOSETIMER_DELAY
@@ -1522,6 +1590,7 @@ __device__ void tcp_process(L& c, DSock* k, int32_t pi) {   // tcp.c:1777-2099
             ch->child_state = 1;
             ch->peer_ip = p->sip; ch->peer_port = p->sport;
             ch->bound = 1; ch->bound_ip = k->bound_ip; ch->bound_port = k->bound_port;
+            dir_put(c, ch);   // (not associated: its listener's key receives for it)
             if (k->nkids >= kKids) { c.H->err |= SHD_TCP_ERR_SOCKETS; return; }
             k->kids[k->nkids++] = ci;
             ch->r_start = p->seq;
@@ -1643,18 +1712,26 @@ __device__ void refill_if_needed(L& c) {   // :130-161, started at t = 0
 }
 __device__ __forceinline__ void consume(uint64_t& rem, uint64_t n) { rem = (n >= rem) ? 0 : rem - n; }
 // the association keys are (protocol, port, peer); general: peer 0:0
+// One pass over the host's directory, four slots' keys loaded before any is
+// tested (the loads do not depend on each other): the first general match in
+// slot order, else the first specific one -- the two walks' result
 __device__ DSock* lookup_socket(L& c, int32_t udp, uint16_t port, uint32_t peer_ip, uint16_t peer_port) {   // :385-403
-    for (int32_t j = 0; j < c.H->nsock; j++) {
-        DSock* k = SK(c, j);
-        if (k->assoc && k->assoc_general && k->udp == udp && k->bound_port == port) return k;
+    const uint4* d = (const uint4*)(c.g->dir + c.s0);
+    const int32_t n = c.H->nsock;
+    const uint32_t kind = kDAssoc | kDGeneral | kDUdp;
+    const uint32_t gen = kDAssoc | kDGeneral | (udp ? kDUdp : 0u), spec = kDAssoc | (udp ? kDUdp : 0u);
+    const uint32_t ports = (uint32_t)port | ((uint32_t)peer_port << 16);
+    int32_t found = -1;
+    for (int32_t b = 0; b < n; b += 4) {
+        const uint4 q[4] = {d[b], d[b + 1], d[b + 2], d[b + 3]};   // (x ports, y peer_ip, z flags)
+#pragma unroll
+        for (int32_t i = 0; i < 4; i++) {
+            if (b + i >= n) break;
+            if ((q[i].z & kind) == gen && (q[i].x & 0xffffu) == port) return SK(c, b + i);
+            if (found < 0 && (q[i].z & kind) == spec && q[i].x == ports && q[i].y == peer_ip) found = b + i;
+        }
     }
-    for (int32_t j = 0; j < c.H->nsock; j++) {
-        DSock* k = SK(c, j);
-        if (k->assoc && !k->assoc_general && k->udp == udp && k->bound_port == port && k->peer_ip == peer_ip &&
-            k->peer_port == peer_port)
-            return k;
-    }
-    return nullptr;
+    return found >= 0 ? SK(c, found) : nullptr;
 }
 // CoDel (router_queue_codel.c:148-267)
 constexpr uint64_t kCodelTarget = 10 * kMs, kCodelInterval = 100 * kMs;
@@ -1898,22 +1975,23 @@ __device__ void if_send_packets(L& c) {   // :519-579, FIFO qdisc
         int32_t pi = -1;
         DSock* ks = nullptr;   // the socket the packet came from
         DSock* drained = nullptr;   // ... left the sendable queue (a closed datagram socket is released after)
-        while (c.g->qdisc_rr && pi < 0 && H->rrq.n) {   // _networkinterface_selectRoundRobin (:466-490)
-            const int32_t si = rg_pop(H->rrq);
+        int32_t* const fifo = c.g->ifq + c.s0;
+        while (c.g->qdisc_rr && pi < 0 && H->ifq_n) {   // _networkinterface_selectRoundRobin (:466-490)
+            const int32_t si = iq_pop(c);
             DSock* k = &c.g->sock[si];
             ks = k;
             pi = sock_remove_output(c, k);
             if (pi >= 0 && !k->udp) tcp_about_to_send(c, k, pi);   // _networkinterface_updatePacketHeader (:457-463)
-            if (sock_peek_out(c, k) >= 0) rg_push(H->rrq, si, H->err);
+            if (sock_peek_out(c, k) >= 0) iq_push(c, si);
             else drained = k;
         }
-        while (pi < 0 && H->fifo.n) {   // _networkinterface_selectFirstInFirstOut (:492-517)
-            const int32_t si = ih_pop(H->fifo, lt);
+        while (!c.g->qdisc_rr && pi < 0 && H->ifq_n) {   // _networkinterface_selectFirstInFirstOut (:492-517)
+            const int32_t si = ih_pop(fifo, H->ifq_n, lt);
             DSock* k = &c.g->sock[si];
             ks = k;
             pi = sock_remove_output(c, k);
             if (pi >= 0 && !k->udp) tcp_about_to_send(c, k, pi);
-            if (sock_peek_out(c, k) >= 0) ih_push(H->fifo, si, lt, H->err);
+            if (sock_peek_out(c, k) >= 0) ih_push(fifo, H->ifq_n, (uint32_t)c.scap, si, lt, H->err);
             else drained = k;
         }
         if (pi < 0) {
@@ -1960,10 +2038,17 @@ __device__ uint16_t random_port(L& c) {   // :1058-1070
 // (network_interface.c:279-301): the protocol's port is taken by a socket
 // associated with no peer (the general key) or with this peer
 __device__ bool port_free(L& c, int32_t udp, uint16_t port, uint32_t peer_ip, uint16_t peer_port) {
-    for (int32_t j = 0; j < c.H->nsock; j++) {
-        const DSock* k = SK(c, j);
-        if (!k->assoc || k->udp != udp || k->bound_port != port) continue;
-        if (k->assoc_general || (k->peer_ip == peer_ip && k->peer_port == peer_port)) return false;
+    const uint4* d = (const uint4*)(c.g->dir + c.s0);
+    const int32_t n = c.H->nsock;
+    const uint32_t want = kDAssoc | (udp ? kDUdp : 0u);
+    for (int32_t b = 0; b < n; b += 4) {
+        const uint4 q[4] = {d[b], d[b + 1], d[b + 2], d[b + 3]};
+#pragma unroll
+        for (int32_t i = 0; i < 4; i++) {
+            if (b + i >= n) break;
+            if ((q[i].z & (kDAssoc | kDUdp)) != want || (q[i].x & 0xffffu) != port) continue;
+            if ((q[i].z & kDGeneral) || (q[i].y == peer_ip && (q[i].x >> 16) == peer_port)) return false;
+        }
     }
     return true;
 }
@@ -2100,6 +2185,7 @@ __device__ int32_t udp_sock_new(L& c) {
     if (si < 0) return -1;
     DSock* k = &c.g->sock[si];
     k->udp = 1;
+    dir_put(c, k);
     k->in_size = c.g->recv_buf;
     k->out_size = c.g->send_buf;
     k->status = DS_ACTIVE | DS_WRITABLE;
@@ -2117,6 +2203,7 @@ __device__ int udp_send_user(L& c, DSock* k, uint32_t n, uint32_t ip, uint16_t p
         k->bound = 1; k->bound_ip = c.H->ip; k->bound_port = bp;
         k->peer_ip = 0; k->peer_port = 0;
         k->assoc = 1; k->assoc_general = 1;
+        dir_put(c, k);
     }
     if (out_space(k) < n) return E_WOULDBLOCK;
     const int32_t pi = pkt_new(c, n);
@@ -2148,12 +2235,14 @@ __device__ void udp_release(L& c, DSock* k) {
     if (!k->udp || !(k->status & DS_CLOSED) || k->out.n || k->outctl.n) return;
     while (k->in.n) pkt_unref(c, rg_pop(k->in));
     k->used = 0;
+    dir_put(c, k);
 }
 // host_closeUser -> descriptor_close -> udp_close -> host_closeDescriptor
 // (host.c:768-771, 571-583): closed, no longer associated
 __device__ void udp_close(L& c, DSock* k) {
     sock_status(c, k, DS_CLOSED, true);
     k->assoc = 0; k->assoc_general = 0;
+    dir_put(c, k);
     udp_release(c, k);
 }
 
@@ -2213,6 +2302,7 @@ __device__ void udp_app_start(L& c, DProc* pr) {
     if (a[0] != 1 && port_free(c, 1, kUdpPort, 0, 0)) {   // bind INADDR_ANY:8998 (host.c:1111-1189)
         l->bound = 1; l->bound_ip = 0; l->bound_port = kUdpPort;
         l->assoc = 1; l->assoc_general = 1;
+        dir_put(c, l);
     }
     app_wait(c, pr, li, 1);   // epoll_ctl ADD, EPOLLIN
     for (uint32_t i = 0; i < a[2]; i++) udp_app_send(c, pr, 0, 0);
@@ -2243,6 +2333,7 @@ __device__ void app_run(L& c, DProc* pr) {
             l->bound = 1; l->bound_ip = 0; l->bound_port = random_free_port(c, 0, 0, 0);   // bind INADDR_ANY:0
             publish_port(c, pr->index, l->bound_port);
             l->assoc = 1; l->assoc_general = 1;
+            dir_put(c, l);
             l->server = 1;   // listen (tcp.c:1486-1494)
             tcp_set_state(c, l, TS_LISTEN);
             pr->step = T_SRV_ACCEPT;
@@ -2331,6 +2422,7 @@ __device__ void app_run(L& c, DProc* pr) {
                 k->bound = 1; k->bound_ip = c.H->ip; k->bound_port = bp;
                 k->peer_ip = ip; k->peer_port = port;
                 k->assoc = 1; k->assoc_general = 0;
+                dir_put(c, k);
             }
             int rc = tcp_connect_error(k);
             if (rc == E_ISCONN && !(k->flags & TF_CONNECT_SIGNALED)) {
@@ -2474,12 +2566,12 @@ __global__ void __launch_bounds__(64) k_tcp_boot(Glob g) {
     if (h >= g.nloc) return;
     Glob gl = g;
     L c{&gl, h, gl.h0 + h, &gl.host[h], 0, h, 0, 0, 0, ~0ull};
+    lane_slots(c);
     sched_task(c, gl.hb_host ? gl.hb_host[h] : gl.hb, K_HEARTBEAT, -1);
     refill_cb(c);
     sched_task(c, kMs, K_REFILL_LO, -1);
-    for (int j = 0; j < kProcs; j++) {
-        const int32_t pi = gl.host_procs[h * kProcs + j];
-        if (pi < 0) break;
+    for (int32_t j = gl.proc_off[h]; j < gl.proc_off[h + 1]; j++) {
+        const int32_t pi = gl.host_procs[j];
         const uint64_t st = gl.proc[pi].start;
         sched_task(c, st > 0 ? st : 1, K_PSTART, pi);
     }
@@ -2808,6 +2900,7 @@ __global__ void __launch_bounds__(64) k_tcp_round(Glob g) {
 #else
     L c{&gl, h, gl.h0 + h, &gl.host[h], 0, h, 0, 0, 0, ~0ull};
 #endif
+    lane_slots(c);
 #ifdef SHD_TCP_PROF
     uint64_t* pf = gl.prof + (size_t)h * 2 * kProf;
     const uint64_t t_lane = clock64();
@@ -2856,6 +2949,72 @@ __global__ void __launch_bounds__(64) k_tcp_round(Glob g) {
 }
 
 #define HCHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "shd_tcp: %s: %s\n", #x, hipGetErrorString(e_)); rc = -5; goto done; } } while (0)
+
+// The reference keeps a socket's retransmit queue in a GHashTable keyed by
+// sequence and clears it through an iterator (_tcp_clearRetransmit,
+// tcp.c:876-897), so the lines of the segments one clear drops -- each
+// segment's SND_TCP_DEQUEUE_RETRANSMIT line and, when that was its last
+// reference, its PDS_DESTROYED line -- come in the table's order.  The device
+// drops them in sequence order and marks those records (kTrIter).  Here one
+// host's records are replayed in their order: every socket (the segments'
+// addresses) gets the table its ENQUEUE / DEQUEUE records describe (GhtOrder:
+// an insert, a removal with or without the resize check), and each run of
+// marked records of one socket at one time is put into that table's order.
+// Nothing else depends on the order within such a run: the packets' status
+// lists, counters and pool slots' contents are the same either way.
+void order_iter_clears(std::vector<TRec>& recs) {
+    struct Key {
+        uint32_t sip, dip, ports;
+        bool operator<(const Key& o) const {
+            return sip != o.sip ? sip < o.sip : dip != o.dip ? dip < o.dip : ports < o.ports;
+        }
+    };
+    std::map<Key, GhtOrder> tables;
+    std::vector<uint32_t> ord;
+    std::vector<TRec> run;
+    const size_t n = recs.size();
+    for (size_t i = 0; i < n;) {
+        TRec& r = recs[i];
+        const Key key{r.sip, r.dip, (uint32_t)r.sport << 16 | r.dport};
+        if (r.flags & kTrUdp) { i++; continue; }
+        if (r.status == S_SND_TCP_ENQUEUE_RETRANSMIT) {
+            GhtOrder& t = tables[key];
+            if ((r.flags & F_SYN) && t.nnodes == 0) t = GhtOrder();   // a connection's first segment: tcp_new's table
+            t.insert(r.seq);
+            i++;
+            continue;
+        }
+        if (r.status != S_SND_TCP_DEQUEUE_RETRANSMIT) { i++; continue; }
+        GhtOrder& t = tables[key];
+        if (!(r.flags & kTrIter)) { t.remove(r.seq, false); i++; continue; }
+        // the run: marked records of this socket at this time, sequences ascending, each
+        // followed by the same packet's PDS_DESTROYED record or by the next marked one
+        size_t j = i;
+        std::vector<std::pair<size_t, size_t>> part;   // [first, end) of each segment's records
+        uint32_t last_seq = 0;
+        while (j < n) {
+            const TRec& a = recs[j];
+            if (a.status != S_SND_TCP_DEQUEUE_RETRANSMIT || !(a.flags & kTrIter) || (a.flags & kTrUdp) ||
+                a.time != r.time || a.sip != r.sip || a.dip != r.dip || a.sport != r.sport || a.dport != r.dport ||
+                (!part.empty() && a.seq <= last_seq))
+                break;
+            size_t e = j + 1;
+            if (e < n && recs[e].status == S_DESTROYED && recs[e].pid == a.pid && recs[e].host_id == a.host_id) e++;
+            part.push_back({j, e});
+            last_seq = a.seq;
+            j = e;
+        }
+        t.order(ord);
+        run.clear();
+        for (uint32_t sq : ord)
+            for (const auto& pe : part)
+                if (recs[pe.first].seq == sq) run.insert(run.end(), recs.begin() + pe.first, recs.begin() + pe.second);
+        if (run.size() == j - i) std::copy(run.begin(), run.end(), recs.begin() + i);   // (else: a record the table lacks; left)
+        for (const auto& pe : part) t.remove(recs[pe.first].seq, true);
+        for (size_t x = i; x < j; x++) recs[x].flags &= ~kTrIter;
+        i = j;
+    }
+}
 
 void ip_str(uint32_t ip, char* b) { snprintf(b, 20, "%u.%u.%u.%u", (ip >> 24) & 255, (ip >> 16) & 255, (ip >> 8) & 255, ip & 255); }
 
@@ -3075,7 +3234,8 @@ enum WsSlot {
     kWsHostProcs, kWsPool, kWsPsack, kWsFreel, kWsEv, kWsCq, kWsMsack, kWsNmsack, kWsMail, kWsNmail, kWsMhead,
     kWsMnext, kWsCtl, kWsIpk, kWsNode, kWsTr, kWsTrs, kWsNextTime, kWsQlog, kWsNqlog, kWsProf, kWsProfRound,
     kWsAppSpec, kWsAppPeer, kWsDestCum, kWsHostClass, kWsIpAll, kWsBwu, kWsBwd, kWsProcPort, kWsPortNew, kWsXsend,
-    kWsXrecv, kWsPmine, kWsPall, kWsXcnt, kWsGmine, kWsGall, kWsPcap, kWsNpcap, kWsPcapSlot, kWsHostHb, kWsSlots
+    kWsXrecv, kWsPmine, kWsPall, kWsXcnt, kWsGmine, kWsGall, kWsPcap, kWsNpcap, kWsPcapSlot, kWsHostHb, kWsSockOff, kWsDir, kWsIfq,
+    kWsProcOff, kWsSlots
 };
 struct TcpWs {
     std::mutex mu;
@@ -3175,6 +3335,49 @@ static hipError_t pcap_drain(TcpPcap& pc, const Glob& g, hipStream_t st) {
     const hipError_t e = hipMemsetAsync(g.npcap, 0, sizeof(uint32_t) * pc.cnt.size(), st);
     if (e != hipSuccess) return e;
     return hipStreamSynchronize(st);
+}
+
+// The socket slots and processes of hosts [h0, h0 + nloc) as ranges: host
+// h0 + i's slots are [so[i], so[i + 1]), its processes hp[po[i] .. po[i + 1])
+// in <process> order.  A host's slots are the sockets it can ever create (a
+// socket is not released in a TCP run): a listener and one child per client
+// process that names it, on whichever engine, for each of its servers; one
+// for each of its clients; kUdpSlots for its datagram process.  The rule
+// reads the whole model, so every engine of a group sizes its own hosts
+// with no exchange.  False: more slots than a socket index holds.
+static bool tcp_host_slots(const shd_tcp_model* m, int32_t h0, int32_t nloc, std::vector<int32_t>& so,
+                           std::vector<int32_t>& po, std::vector<int32_t>& hp, uint32_t* max_procs) {
+    const int32_t P = m->n_procs;
+    std::vector<int64_t> cap(nloc, 0);
+    std::vector<int32_t> np(nloc, 0), nclients(P > 0 ? P : 1, 0);
+    for (int32_t k = 0; k < P; k++)
+        if (m->proc_peer[k] >= 0) nclients[m->proc_peer[k]]++;
+    for (int32_t k = 0; k < P; k++) {
+        const int32_t i = m->proc_host[k] - h0;
+        if (i < 0 || i >= nloc) continue;   // another engine's
+        np[i]++;
+        if (m->proc_app && m->proc_app[k] >= 0) cap[i] += kUdpSlots;
+        else if (m->proc_peer[k] >= 0) cap[i] += 1;
+        else cap[i] += 1 + (int64_t)nclients[k];
+    }
+    so.assign((size_t)nloc + 1, 0);
+    po.assign((size_t)nloc + 1, 0);
+    int64_t tot = 0;
+    *max_procs = 0;
+    for (int32_t i = 0; i < nloc; i++) {
+        tot += cap[i];
+        if (tot > (int64_t)0x7fffffff - (int64_t)kDirPad) return false;
+        so[i + 1] = (int32_t)tot;
+        po[i + 1] = po[i] + np[i];
+        *max_procs = std::max<uint32_t>(*max_procs, (uint32_t)np[i]);
+    }
+    hp.assign((size_t)po[nloc], -1);
+    std::vector<int32_t> at(po.begin(), po.end() - 1);
+    for (int32_t k = 0; k < P; k++) {
+        const int32_t i = m->proc_host[k] - h0;
+        if (i >= 0 && i < nloc) hp[at[i]++] = k;
+    }
+    return true;
 }
 
 static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, shd_tcp_result** out,
@@ -3314,7 +3517,7 @@ static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, s
     memset(&g, 0, sizeof(g));
     std::vector<DHost> hh(nloc);
     std::vector<DProc> pp(P > 0 ? P : 1);
-    std::vector<int32_t> hp((size_t)nloc * kProcs, -1);
+    std::vector<int32_t> hp, hpo, so;   // this engine's hosts: their processes and socket slots as ranges
     shd_tcp_result* res = (shd_tcp_result*)calloc(1, sizeof(shd_tcp_result));
     double* d_lat = nullptr; double* d_rel = nullptr;
     uint32_t* d_spec = nullptr; int32_t* d_apeer = nullptr; double* d_cum = nullptr; uint8_t* d_cls = nullptr;
@@ -3358,12 +3561,12 @@ static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, s
         pr.host = m->proc_host[k]; pr.index = k; pr.peer = m->proc_peer[k]; pr.start = m->proc_start[k];
         pr.fd = pr.listenfd = pr.wait_fd = -1;
         pr.app = app_of(k);
-        if (pr.host < h0 || pr.host >= h0 + nloc) continue;   // another engine's
-        int32_t* slot = &hp[(size_t)(pr.host - h0) * kProcs];
-        int j = 0;
-        while (j < kProcs && slot[j] >= 0) j++;
-        if (j == kProcs) { free(res); return -22; }
-        slot[j] = k;
+    }
+    {
+        uint32_t mp = 0;
+        if (!tcp_host_slots(m, h0, nloc, so, hpo, hp, &mp)) { free(res); return -22; }
+        res->max_host_procs = mp;
+        res->sock_bytes = sizeof(DSock) * (uint64_t)so[nloc];
     }
 
     {   // host_of_ip's table: at most half full; an address's first host wins (host order)
@@ -3391,7 +3594,6 @@ static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, s
     g.recv_buf = m->recv_buf; g.send_buf = m->send_buf; g.tcp_window = m->tcp_window;
     if (m->qdisc > 1) { free(res); return -22; }
     g.qdisc_rr = m->qdisc;
-    g.spk = any_udp ? 2 * kSock : kSock;   // (the qdisc queues hold 2 * kSock sockets)
     if (any_udp) {
         g.udp_payload = m->udp_payload;
         g.n_classes = m->n_classes;
@@ -3494,12 +3696,29 @@ static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, s
     g.lat = d_lat; g.rel = d_rel; g.hv = d_hv; g.V = V; g.pool_cap = pool_cap;
     HCHECK(ws_alloc(ws, kWsHost, &g.host, sizeof(DHost) * nloc));
     HCHECK(hipMemcpy(g.host, hh.data(), sizeof(DHost) * nloc, hipMemcpyHostToDevice));
-    HCHECK(ws_alloc(ws, kWsSock, &g.sock, sizeof(DSock) * (size_t)nloc * g.spk));
-    HCHECK(hipMemset(g.sock, 0, sizeof(DSock) * (size_t)nloc * g.spk));
+    {
+        const size_t ns = (size_t)so[nloc];
+        int32_t *d_so = nullptr, *d_hpo = nullptr;
+        HCHECK(ws_alloc(ws, kWsSock, &g.sock, sizeof(DSock) * ns));
+        HCHECK(hipMemset(g.sock, 0, sizeof(DSock) * ns));
+        HCHECK(ws_alloc(ws, kWsSockOff, &d_so, sizeof(int32_t) * so.size()));
+        HCHECK(hipMemcpy(d_so, so.data(), sizeof(int32_t) * so.size(), hipMemcpyHostToDevice));
+        g.sock_off = d_so;
+        HCHECK(ws_alloc(ws, kWsDir, &g.dir, sizeof(DKey) * (ns + kDirPad)));
+        HCHECK(hipMemset(g.dir, 0, sizeof(DKey) * (ns + kDirPad)));
+        HCHECK(ws_alloc(ws, kWsIfq, &g.ifq, sizeof(int32_t) * ns));
+        HCHECK(ws_alloc(ws, kWsProcOff, &d_hpo, sizeof(int32_t) * hpo.size()));
+        HCHECK(hipMemcpy(d_hpo, hpo.data(), sizeof(int32_t) * hpo.size(), hipMemcpyHostToDevice));
+        g.proc_off = d_hpo;
+    }
     HCHECK(ws_alloc(ws, kWsProc, &g.proc, sizeof(DProc) * pp.size()));
     HCHECK(hipMemcpy(g.proc, pp.data(), sizeof(DProc) * pp.size(), hipMemcpyHostToDevice));
-    HCHECK(ws_alloc(ws, kWsHostProcs, &g.host_procs, sizeof(int32_t) * hp.size()));
-    HCHECK(hipMemcpy(g.host_procs, hp.data(), sizeof(int32_t) * hp.size(), hipMemcpyHostToDevice));
+    {
+        int32_t* d_hp = nullptr;
+        HCHECK(ws_alloc(ws, kWsHostProcs, &d_hp, sizeof(int32_t) * hp.size()));
+        if (!hp.empty()) HCHECK(hipMemcpy(d_hp, hp.data(), sizeof(int32_t) * hp.size(), hipMemcpyHostToDevice));
+        g.host_procs = d_hp;
+    }
     HCHECK(ws_alloc(ws, kWsPool, &g.pool, sizeof(DPkt) * (size_t)nloc * pool_cap));
     HCHECK(ws_alloc(ws, kWsPsack, &g.psack, sizeof(int32_t) * kPktSack * (size_t)nloc * pool_cap));
     HCHECK(ws_alloc(ws, kWsFreel, &g.freel, sizeof(int32_t) * (size_t)nloc * pool_cap));
@@ -3879,6 +4098,7 @@ static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, s
         res->events += hout[i].events;
         res->deliveries += hout[i].deliveries;
         res->error |= hout[i].err;
+        res->max_host_sockets = std::max<uint32_t>(res->max_host_sockets, (uint32_t)hout[i].nsock);
     }
     if (g.node) {
         res->node_k = g.node_k;
@@ -3899,6 +4119,7 @@ static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, s
                 HCHECK(hipMemcpy(recs.data(), g.tr + (size_t)i * kTr, sizeof(TRec) * hout[i].ntr, hipMemcpyDeviceToHost));
             if (hout[i].ntrs)
                 HCHECK(hipMemcpy(sk.data(), g.trs + (size_t)i * kTrSack, sizeof(int32_t) * hout[i].ntrs, hipMemcpyDeviceToHost));
+            order_iter_clears(recs);
             for (const TRec& r : recs) format_line(text, r, sk.data() + r.sack_off, h0 + i);
             res->n_lines += hout[i].ntr;
         }

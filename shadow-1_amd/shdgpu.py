@@ -222,11 +222,14 @@ class TcpResult(C.Structure):
                 ("setup_ms", C.c_double), ("results_ms", C.c_double), ("teardown_ms", C.c_double),
                 ("first_host", C.c_int32), ("n_local_hosts", C.c_int32),
                 ("pcap_records", C.c_void_p), ("pcap_off", P(C.c_uint64)), ("pcap_drains", C.c_uint64),
-                ("pcap_ring_peak", C.c_uint32), ("_pad11", C.c_uint32)]
+                ("pcap_ring_peak", C.c_uint32), ("_pad11", C.c_uint32),
+                ("max_host_sockets", C.c_uint32), ("max_host_procs", C.c_uint32), ("sock_bytes", C.c_uint64)]
 
 
 TCP_TRACE_STATUS, TCP_TRACE_NODE = 1, 2   # shd_tcp_run's trace bits
 TCP_ERR_FIRST_TOUCH = 512                  # SHD_TCP_ERR_FIRST_TOUCH (include/shdtcp.h)
+TCP_SOCK_BYTES = 141888                     # SHD_TCP_SOCK_BYTES: device bytes of one socket slot
+TCP_ERR_SOCKETS = 8                        # SHD_TCP_ERR_SOCKETS: more sockets than the host's slots / a listener's 8 children
 TCP_ERR_PCAP = 1024                        # SHD_TCP_ERR_PCAP: a capture ring filled between two drains
 
 # shd_pcap_rec (include/shdtcp.h): one captured packet; addresses and ports in host byte order

@@ -395,3 +395,33 @@ def mixed_transport_model(n_hosts: int, n_vertices: int, *, seed: int = 1, end_s
         apps.append(k)
     udp = dict(apps=apps, specs=specs, app_peer=app_peer, payload=payload)
     return g, m, ips, procs, peers, nb, udp
+
+
+def tcp_hub_model(n_hubs: int, clients_per_hub: int, n_vertices: int, *, seed: int = 1, end_s: int = 20,
+                  nbytes: int = 100000, loss_max: float = 0.0, bw_down=10240, bw_up=10240):
+    """The TCP path's hub model (include/shdtcp.h): n_hubs server hosts, each
+    talked to by clients_per_hub client hosts -- the shape of a relay or a web
+    server.  The hosts come in n_hubs groups of 1 + clients_per_hub: the hub
+    first (so the hubs' lanes spread over the blocks), then its clients; host
+    h sits on vertex h * V // H.  Hub j runs clients_per_hub echo servers
+    (test_tcp.c serves one peer per server), server i from 1 s + i ns; the
+    i-th client host of group j runs one client of it from 2 s + (j *
+    clients_per_hub + i) us, so every client starts a second after its server
+    and no two at the same time.  A hub then holds 2 * clients_per_hub sockets
+    and every client host one.  Addresses are 11.0.0.1 upwards (no .0 / .255
+    octet).  Returns (graph, model, ips, procs, peers, nbytes)."""
+    n, c = int(n_hubs), int(clients_per_hub)
+    G = 1 + c
+    H = n * G
+    g = geometric_graph(n_vertices, seed=seed, loss_max=loss_max)
+    hv = (np.arange(H, dtype=np.int64) * n_vertices // H).astype(np.int32)
+    m = phold_model(hv, end_time=end_s * S.SHD_SEC, seed=seed, load=0, bw_down=bw_down, bw_up=bw_up)
+    ips, ip = [], (11 << 24) + 1
+    while len(ips) < H:
+        if (ip & 255) not in (0, 255):
+            ips.append(ip)
+        ip += 1
+    procs = [(j * G, S.SHD_SEC + i) for j in range(n) for i in range(c)]
+    procs += [(j * G + 1 + i, 2 * S.SHD_SEC + (j * c + i) * 1000) for j in range(n) for i in range(c)]
+    peers = [-1] * (n * c) + list(range(n * c))
+    return g, m, ips, procs, peers, nbytes
