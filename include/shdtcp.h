@@ -15,6 +15,20 @@
  * reference's loop runs them (shd_tcp_model.bootstrap_end / host_heartbeat;
  * tests/test_tcp_options_gpu.py against tests/golden/ref_tcp_options.json).
  *
+ * What a run says about its connections without tracing: with
+ * SHD_TCP_OPT_FLOWS in shd_tcp_model.options, one flow record (shd_tcp_flow)
+ * for every TCP connection endpoint -- when it opened, was established, last
+ * delivered payload and sent its FIN, what it created, retransmitted and lost
+ * and where -- written by the owning host's lane as the run goes and gathered
+ * on the device at the end (shd_tcp_result_flows; tests/test_tcp_flows_gpu.py
+ * against tests/golden/ref_tcp_flows.json).  A client's completion time is
+ * t_last_delivered once bytes_delivered == tcp_bytes.  test_tcp.c closes
+ * right after its last read, so t_fin equals it -- unless the socket still
+ * held output at the close (the FIN follows once that has drained), or the
+ * server's FIN overtook retransmitted data (the client's answer to it carries
+ * FIN and comes before the last delivery): 6 of the fixture's 97 completed
+ * clients.
+ *
  * A host's shape comes from the model.  Its socket slots are the sockets it
  * can ever create -- a socket is not released in a TCP run: for each of its
  * server processes the listener and one child per client process that names
@@ -71,7 +85,7 @@ typedef struct shd_tcp_model {
                                          set SHD_TCP_ERR_POOL                             */
     uint32_t qdisc;                   /* --interface-qdisc (options.c:162): 0 fifo, 1 rr
                                          (network_interface.c:466-517)                    */
-    uint32_t _pad;
+    uint32_t options;                 /* SHD_TCP_OPT_* bits; the others are reserved and ignored */
     /* A built path cache of this model's graph (shdgpu.h shd_pc_create: an
      * undirected graph, the hosts' vertices attached), or NULL.  Set: every
      * path query of the run goes to the cache's device tables under the lazy
@@ -252,6 +266,59 @@ typedef struct shd_tcp_result {
     uint64_t sock_bytes;
 } shd_tcp_result;
 
+/* One TCP connection endpoint of a run with SHD_TCP_OPT_FLOWS: every TCP
+ * socket that ever created a packet -- a connecting socket, and a listener's
+ * child from its SYN+ACK on; listeners and datagram sockets have none.  Times
+ * are ns, 0: never.  Every field but the last five is counted where the
+ * reference raises a packet status (packet_addDeliveryStatus) or sets the
+ * state, so it can be read off a traced run's [STATUS] lines
+ * (tests/tcp_flow_expect.py):
+ *   t_open            the socket's first SND_CREATED (tcp.c:791-835)
+ *   t_established     its _tcp_setState(ESTABLISHED) (tcp.c:1865, 1887)
+ *   t_last_delivered, bytes_delivered
+ *                     RCV_SOCKET_DELIVERED (tcp.c:2226, 2266): the last one's
+ *                     time, the payload of all of them
+ *   t_fin             the first SND_CREATED of a packet carrying FIN
+ *   packets_created, bytes_created
+ *                     SND_CREATED: count and payload (a retransmission sends
+ *                     the same packet again and is not counted again)
+ *   retransmitted     SND_TCP_RETRANSMITTED (tcp.c:1060)
+ *   inet_dropped      INET_DROPPED of its packets (worker.c:281-290)
+ *   socket_dropped    RCV_SOCKET_DROPPED of packets addressed to it
+ *   router_dropped    ROUTER_DROPPED, at this host, of packets addressed to
+ *                     this endpoint's 4-tuple.  The lane finds the record by
+ *                     the 4-tuple among its host's records (what the
+ *                     interface's lookup and a listener's child list give while
+ *                     the socket lives, and a closed child still: the
+ *                     reference raises the status for such a packet too); a
+ *                     packet addressed to no record is counted nowhere
+ * role: 0 its first packet is a SYN without ACK (a connecting socket), 1 a
+ * listener's child.  proc: the connecting process, or for a child the server
+ * process that listens.  local_* / peer_*: the addresses its packets carry
+ * (host byte order).
+ * state, cwnd, ssthresh, srtt, rttvar are the socket's values when the run
+ * ends (state: 0 CLOSED, 1 LISTEN, 2 SYNSENT, 3 SYNRECEIVED, 4 ESTABLISHED,
+ * 5 FINWAIT1, 6 FINWAIT2, 7 CLOSING, 8 TIMEWAIT, 9 CLOSEWAIT, 10 LASTACK, the
+ * order of tcp.c's enum TCPState; cwnd and ssthresh in segments; srtt and
+ * rttvar in ms).  Nothing
+ * the reference build prints pins these five: they are the device's own and
+ * the tests check only that they do not depend on tracing or the path mode. */
+typedef struct shd_tcp_flow {
+    int32_t host, proc;               /* the model's host index; process index      */
+    uint32_t local_ip, peer_ip;
+    uint16_t local_port, peer_port;
+    uint8_t role, state;
+    uint16_t _pad;
+    uint64_t t_open, t_established, t_last_delivered, t_fin;
+    uint64_t bytes_delivered, packets_created, bytes_created;
+    uint64_t retransmitted, inet_dropped, socket_dropped, router_dropped;
+    uint32_t cwnd, ssthresh;
+    int32_t srtt, rttvar;
+} shd_tcp_flow;
+
+/* shd_tcp_model.options */
+enum { SHD_TCP_OPT_FLOWS = 1 };
+
 /* device bytes of one socket slot (its buffers, queues, SACK and retransmit
  * state at their fixed capacities) */
 #define SHD_TCP_SOCK_BYTES 141888
@@ -282,6 +349,17 @@ enum {
  * and released by shd_tcp_result_free. */
 int shd_tcp_run(const shd_tcp_model* m, int32_t trace, shd_tcp_result** out);
 void shd_tcp_result_free(shd_tcp_result* r);
+
+/* The flow records of the hosts this result covers (a result of shd_tcp_run /
+ * shd_tcp_run_group only): by host index, then by the socket's slot within its
+ * host (creation order), so a group's ranks concatenated in rank order equal
+ * the one-engine array; a connection across ranks has one record on each
+ * side.  *recs NULL and *n 0 when the model did not set SHD_TCP_OPT_FLOWS.
+ * Owned by the result.  Returns 0, -22 for a NULL argument.  Without the
+ * option a run allocates nothing for them, launches nothing extra and runs the
+ * rounds as before; a rerun from the start (first_touch_reruns) starts the
+ * records again with it. */
+int shd_tcp_result_flows(const shd_tcp_result* r, const shd_tcp_flow** recs, uint64_t* n);
 
 /* The same model on a group of engines, one per process and GPU (shdgpu.h
  * shd_comm: RCCL, or the host-memory transport for several processes on one

@@ -31,7 +31,9 @@
 // sockets and processes a host has comes from the model (tcp_host_slots):
 // its socket slots, their directory (DKey) and its interface's queue are
 // ranges of engine-wide arrays, so a hub host with dozens of sockets runs
-// beside hosts that hold one.
+// beside hosts that hold one.  With SHD_TCP_OPT_FLOWS a flow record per TCP
+// connection endpoint is kept beside the socket slots (DFlow, flow_status)
+// and gathered by a kernel at the end (k_tcp_flow_*).
 //
 // The work is branchy per-host control flow with a few events per host and
 // round: latency-bound by design ("TCP"); it shares nothing with
@@ -277,6 +279,21 @@ struct DHost {
     uint64_t trk[2 * kTrk];
 };
 struct CqEnt { uint64_t ts; uint32_t len; int32_t pkt; };
+// A socket slot's flow record as the run keeps it (shd_tcp_model.options &
+// SHD_TCP_OPT_FLOWS; shd_tcp_flow's pinned fields): Glob::flow, one per slot
+// beside the socket, not in it.  Written by the slot's host's lane only, with
+// plain stores; packets_created != 0 says the slot has a record, and from
+// then on the addresses are its first packet's.  Datagram sockets and
+// listeners never write theirs, so a released datagram slot's stays zero.
+struct DFlow {
+    uint64_t t_open, t_established, t_last_delivered, t_fin;
+    uint64_t bytes_delivered, packets_created, bytes_created;
+    uint64_t retransmitted, inet_dropped, socket_dropped, router_dropped;
+    uint32_t local_ip, peer_ip;
+    uint16_t local_port, peer_port;
+    uint32_t role;
+};
+static_assert(sizeof(DFlow) == 104, "a flow record beside each socket slot");
 
 // the round driver's device-side state (the host only reads it between batches)
 struct TCtl {
@@ -397,6 +414,11 @@ struct Glob {
     // host's own heartbeat interval (null: hb for every host)
     uint64_t boot_end;
     const uint64_t* hb_host;    // [nloc]
+    // flow records (SHD_TCP_OPT_FLOWS): flow [sock_off[nloc]], each slot's
+    // record, null without the option; flow_on says they are kept.  stat_on is
+    // what pkt_status tests: trace | flow_on << 1.
+    DFlow* flow;
+    uint32_t flow_on, stat_on;
 };
 struct XSegHead { uint32_t n, nsack, err, _pad[13]; };   // 64 B, then xcap Mails, then xsack_cap SACK words
 static_assert(sizeof(XSegHead) == 64, "segment header");
@@ -636,11 +658,20 @@ __device__ bool sched_task(L& c, uint64_t delay, uint32_t kind, int32_t obj) {
 }
 
 // ------------------------------------------------------------ packets and their lines
-__device__ void pkt_status(L& c, int32_t pi, uint8_t st, uint32_t trflags = 0) {   // packet_addDeliveryStatus (packet.c:647-659)
+// k: the socket raising the status, at the sites a flow record counts (flow_status)
+__device__ void flow_status(L& c, const DSock* k, const DPkt* p, uint8_t st);
+__device__ void pkt_status(L& c, int32_t pi, uint8_t st, uint32_t trflags = 0,
+                           const DSock* k = nullptr) {   // packet_addDeliveryStatus (packet.c:647-659)
     DPkt* p = PK(c, pi);
     DHost* H = c.H;
     if (st == S_SND_TCP_RETRANSMITTED) p->xflags |= kXRetx;   // packet_getDeliveryStatus's OR of every status
-    if (!c.g->trace) return;   // the list is read by the lines only
+    // one word says what a status feeds besides the packet: the lines (1) and
+    // the flow records (2).  A run with neither leaves here as it did when the
+    // word was Glob::trace alone: the records cost it no test of their own.
+    const uint32_t on = c.g->stat_on;
+    if (__builtin_expect(!on, 1)) return;   // (the untraced run's path falls through)
+    if (on & 2u) flow_status(c, k, p, st);
+    if (!(on & 1u)) return;   // the list is read by the lines only
     if (p->nst < kSt) p->st[p->nst++] = st;
     else H->err |= SHD_TCP_ERR_TRACE;   // a line would lose statuses: fail, never truncate
     if (H->ntr >= kTr) { H->err |= SHD_TCP_ERR_TRACE; return; }
@@ -690,6 +721,67 @@ __device__ void pkt_unref(L& c, int32_t i) {   // packet.c:194-201
     if (--p->refs == 0) {
         pkt_status(c, i, S_DESTROYED);
         c.g->freel[(size_t)c.h * c.g->pool_cap + c.H->nfree++] = i;
+    }
+}
+
+// ------------------------------------------------------------ flow records (shd_tcp_flow)
+__device__ __forceinline__ DFlow* flow_of(const L& c, const DSock* k) { return &c.g->flow[sidx(c, k)]; }
+// the record a packet arriving at this host is addressed to, by its 4-tuple
+// among the host's records: what the interface's lookup and the listener's
+// child list give while the socket lives (lookup_socket, tcp_process), and a
+// closed child, which has left that list, still.  Null: no such record.
+__device__ DFlow* flow_addressed(L& c, const DPkt* p) {
+    if (p->xflags & kXUdp) return nullptr;
+    DFlow* f = c.g->flow + c.s0;
+    for (int32_t j = 0; j < c.H->nsock; j++, f++)
+        if (f->packets_created && f->local_port == p->dport && f->peer_port == p->sport && f->peer_ip == p->sip &&
+            f->local_ip == p->dip)
+            return f;
+    return nullptr;
+}
+// The record points: pkt_status hands every status here when the run keeps
+// flow records, with the socket that raised it where the field needs one (k;
+// null elsewhere, and for datagrams).  Each field is counted where the
+// reference raises the status it is defined by.
+__device__ void flow_status(L& c, const DSock* k, const DPkt* p, uint8_t st) {
+    DFlow* f;
+    switch (st) {
+    case S_SND_CREATED:   // tcp.c:791-835: the record starts with the socket's first packet
+        if (!k) return;
+        f = flow_of(c, k);
+        if (!f->packets_created) {
+            f->t_open = c.now;
+            f->local_ip = p->sip; f->peer_ip = p->dip; f->local_port = p->sport; f->peer_port = p->dport;
+            f->role = ((p->flags & F_SYN) && !(p->flags & F_ACK)) ? 0u : 1u;
+        }
+        f->packets_created++;
+        f->bytes_created += p->len;
+        if ((p->flags & F_FIN) && !f->t_fin) f->t_fin = c.now;
+        return;
+    case S_SND_TCP_RETRANSMITTED:   // tcp.c:1060
+        if (k) flow_of(c, k)->retransmitted++;
+        return;
+    case S_INET_DROPPED:   // worker.c:281-290, the sending socket in hand
+        if (k && !k->udp) flow_of(c, k)->inet_dropped++;
+        return;
+    case S_RCV_SOCKET_DELIVERED:   // tcp.c:2226, 2266
+        if (!k) return;
+        f = flow_of(c, k);
+        f->t_last_delivered = c.now;
+        f->bytes_delivered += p->len;
+        return;
+    case S_RCV_SOCKET_DROPPED:   // while socket k processed the packet (tcp.c:1597-1660, 1777-2099): a
+                                 // listener that found no child for it has no record of its own
+        if (!k) return;
+        f = k->server ? flow_addressed(c, p) : flow_of(c, k);
+        if (f) f->socket_dropped++;
+        return;
+    case S_ROUTER_DROPPED:   // at this host's router (router_queue_codel.c's drop): no socket in hand
+        f = flow_addressed(c, p);
+        if (f) f->router_dropped++;
+        return;
+    default:
+        return;
     }
 }
 
@@ -1323,7 +1415,7 @@ __device__ int32_t tcp_create_packet(L& c, DSock* k, uint32_t flags, uint32_t le
     if (pi < 0) return -1;
     DPkt* p = PK(c, pi);
     p->flags = flags; p->sip = sip; p->sport = sport; p->dip = dip; p->dport = dport; p->seq = seq;
-    pkt_status(c, pi, S_SND_CREATED);
+    pkt_status(c, pi, S_SND_CREATED, 0, k);
     if (seq > 0) k->s_next++;
     return pi;
 }
@@ -1337,7 +1429,7 @@ __device__ void tcp_retransmit_packet(L& c, DSock* k, uint32_t seq) {   // tcp.c
     if (space_out(k) > 0) sock_status(c, k, DS_WRITABLE, true);
     tcp_set_rto_timer(c, k, c.now);
     tcp_buffer_out(c, k, pi);
-    pkt_status(c, pi, S_SND_TCP_RETRANSMITTED);
+    pkt_status(c, pi, S_SND_TCP_RETRANSMITTED, 0, k);
     k->retx_count++;
     pkt_unref(c, pi);
 }
@@ -1457,6 +1549,8 @@ __device__ void tcp_set_state(L& c, DSock* k, int st) {   // tcp.c:607-693
         sock_status(c, k, DS_ACTIVE, true);
     } else if (st == TS_ESTABLISHED) {
         k->flags |= TF_WAS_ESTABLISHED;
+        // (tcp.c:1865, 1887 raise no packet status: the one record point outside flow_status, twice a connection)
+        if (__builtin_expect(c.g->flow_on != 0, 0) && !flow_of(c, k)->t_established) flow_of(c, k)->t_established = c.now;
         sock_status(c, k, DS_ACTIVE | DS_WRITABLE, true);
     } else if (st == TS_CLOSED) {
         tcp_clear_retransmit(c, k, 0xffffffffu);
@@ -1495,7 +1589,7 @@ __device__ uint32_t tcp_data_processing(L& c, DSock* k, int32_t pi) {   // tcp.c
     uint32_t fl = 0;
     if (p->seq >= k->r_next + k->r_window) {
         fl |= PF_PROCESSED;
-        pkt_status(c, pi, S_RCV_SOCKET_DROPPED);
+        pkt_status(c, pi, S_RCV_SOCKET_DROPPED, 0, k);
     } else if (p->seq >= k->r_next) {
         fl |= PF_PROCESSED;
         const bool is_next = p->seq == k->r_next;
@@ -1524,7 +1618,7 @@ __device__ uint32_t tcp_data_processing(L& c, DSock* k, int32_t pi) {   // tcp.c
             tcp_buffer_in(c, k, pi);
             fl |= PF_DATA_RECEIVED;
         } else {
-            pkt_status(c, pi, S_RCV_SOCKET_DROPPED);
+            pkt_status(c, pi, S_RCV_SOCKET_DROPPED, 0, k);
         }
     }
     return fl;
@@ -1670,16 +1764,16 @@ __device__ void tcp_process(L& c, DSock* k, int32_t pi) {   // tcp.c:1777-2099
         if ((p->flags & F_FIN) && (p->flags & F_ACK)) { fl |= PF_PROCESSED; tcp_set_state(c, k, TS_CLOSED); return; }
         break;
     default:
-        pkt_status(c, pi, S_RCV_SOCKET_DROPPED);
+        pkt_status(c, pi, S_RCV_SOCKET_DROPPED, 0, k);
         return;
     }
     if (k->state == TS_LISTEN) {
-        if (!(fl & PF_PROCESSED)) pkt_status(c, pi, S_RCV_SOCKET_DROPPED);
+        if (!(fl & PF_PROCESSED)) pkt_status(c, pi, S_RCV_SOCKET_DROPPED, 0, k);
         return;
     }
     if (p->len > 0 && !(k->error & TE_RECEIVE_EOF)) fl |= tcp_data_processing(c, k, pi);
     if (p->flags & F_ACK) fl |= tcp_ack_processing(c, k, pi);
-    if (!(fl & PF_PROCESSED)) { pkt_status(c, pi, S_RCV_SOCKET_DROPPED); return; }
+    if (!(fl & PF_PROCESSED)) { pkt_status(c, pi, S_RCV_SOCKET_DROPPED, 0, k); return; }
     if (p->nsack) tally_mark_sacked(k->tally, PSK(c, pi), p->nsack, c.H->err);
     k->r_last_ts = p->tsval;
     if (p->tsecho && k->backoff == 0) tcp_update_rtt(c, k, p->tsecho);
@@ -1756,7 +1850,7 @@ __device__ uint64_t cq_law(uint32_t count, uint64_t ts) {
     return (uint64_t)round(((double)(ts + kCodelInterval)) / sqrt((double)count));
 }
 __device__ void cq_drop(L& c, const CqEnt& e) {
-    pkt_status(c, e.pkt, S_ROUTER_DROPPED);
+    pkt_status(c, e.pkt, S_ROUTER_DROPPED);   // (its flow record: found by the packet's 4-tuple, flow_status)
     pkt_unref(c, e.pkt);
 }
 __device__ bool cq_dequeue(L& c, CqEnt& out) {
@@ -1961,7 +2055,7 @@ __device__ void worker_send_packet(L& c, int32_t pi, DSock* ks) {   // worker.c:
         m->pkt.inq = 0;   // the copy is in no queue of the receiver
         c.g->mnext_out[slot] = atomicExch(&c.g->mhead_out[dl], (int32_t)slot);   // the receiver's list
     } else {
-        pkt_status(c, pi, S_INET_DROPPED);
+        pkt_status(c, pi, S_INET_DROPPED, 0, ks);
     }
 }
 __device__ void if_send_packets(L& c) {   // :519-579, FIFO qdisc
@@ -2117,7 +2211,7 @@ __device__ int host_receive(L& c, DSock* k, uint64_t n, uint64_t& copied) {   //
         const uint64_t cl = pb < remaining ? pb : remaining;
         total += cl; remaining -= cl;
         if (cl >= pb) {
-            pkt_status(c, k->partial, S_RCV_SOCKET_DELIVERED);
+            pkt_status(c, k->partial, S_RCV_SOCKET_DELIVERED, 0, k);
             pkt_unref(c, k->partial);
             k->partial = -1;
             k->partial_off = 0;
@@ -2132,7 +2226,7 @@ __device__ int host_receive(L& c, DSock* k, uint64_t n, uint64_t& copied) {   //
         const uint64_t cl = plen < remaining ? plen : remaining;
         total += cl; remaining -= cl;
         if (cl < plen) { k->partial = pi; k->partial_off = (uint32_t)cl; break; }
-        pkt_status(c, pi, S_RCV_SOCKET_DELIVERED);
+        pkt_status(c, pi, S_RCV_SOCKET_DELIVERED, 0, k);
         pkt_unref(c, pi);
     }
     if (k->in_len > 0 || k->partial >= 0) {
@@ -2850,6 +2944,75 @@ __global__ void k_tcp_ports_pack(Glob g, uint64_t* __restrict__ mine) {
     for (uint32_t i = threadIdx.x; i < n && i < g.pcap; i += blockDim.x) mine[1 + i] = g.port_new[i];
 }
 
+// The run's flow records gathered at its end (SHD_TCP_OPT_FLOWS): the slots
+// that have one compacted into shd_tcp_flow records ordered by host, then by
+// slot -- a count per host, a prefix over the hosts, then one thread per slot
+// writing its record.  Reads the slots' DFlow and the scalar head of their
+// DSock only: nothing of the 139-KB slots goes to the host.
+constexpr int kFlowScan = 1024;
+__global__ void k_tcp_flow_count(Glob g, uint32_t* __restrict__ cnt) {   // one thread per host
+    const int32_t h = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (h >= g.nloc) return;
+    uint32_t n = 0;
+    for (int32_t s = g.sock_off[h]; s < g.sock_off[h + 1]; s++) n += g.flow[s].packets_created != 0;
+    cnt[h] = n;
+}
+// off[h]: the records of the hosts before h; off[n]: all of them (one block:
+// each thread sums a contiguous run of hosts, the runs' sums are scanned in LDS)
+__global__ void __launch_bounds__(kFlowScan) k_tcp_flow_scan(const uint32_t* __restrict__ cnt,
+                                                             uint32_t* __restrict__ off, int32_t n) {
+    __shared__ uint32_t part[kFlowScan];
+    const int32_t t = (int32_t)threadIdx.x, per = (n + kFlowScan - 1) / kFlowScan;
+    const int32_t a = t * per < n ? t * per : n, b = a + per < n ? a + per : n;
+    uint32_t s = 0;
+    for (int32_t i = a; i < b; i++) s += cnt[i];
+    part[t] = s;
+    __syncthreads();
+    for (int32_t d = 1; d < kFlowScan; d <<= 1) {
+        const uint32_t v = t >= d ? part[t - d] : 0u;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    uint32_t base = part[t] - s;
+    for (int32_t i = a; i < b; i++) { off[i] = base; base += cnt[i]; }
+    if (t == kFlowScan - 1) off[n] = part[t];
+}
+__global__ void k_tcp_flow_write(Glob g, const uint32_t* __restrict__ off, shd_tcp_flow* __restrict__ out,
+                                 int32_t ns) {   // one thread per socket slot
+    const int32_t s = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (s >= ns) return;
+    const DFlow f = g.flow[s];
+    if (!f.packets_created) return;
+    const DSock* k = &g.sock[s];
+    const int32_t h = k->host;   // (a slot with a record was taken by sock_new: its lane's host)
+    if (h < 0 || h >= g.nloc || s < g.sock_off[h] || s >= g.sock_off[h + 1]) return;
+    uint32_t at = off[h];
+    for (int32_t j = g.sock_off[h]; j < s; j++) at += g.flow[j].packets_created != 0;
+    shd_tcp_flow r;
+    r.host = g.h0 + h;
+    // the host's process that holds the socket: the client whose descriptor it
+    // is, or for a child the server whose listener is its parent (DSock::proc
+    // is the epoll watch, set and cleared as the process waits)
+    r.proc = -1;
+    for (int32_t j = g.proc_off[h]; j < g.proc_off[h + 1]; j++) {
+        const DProc* pr = &g.proc[g.host_procs[j]];
+        if (pr->app >= 0) continue;
+        if (k->child ? (pr->peer < 0 && pr->listenfd == k->parent) : (pr->peer >= 0 && pr->fd == s)) {
+            r.proc = pr->index;
+            break;
+        }
+    }
+    r.local_ip = f.local_ip; r.peer_ip = f.peer_ip; r.local_port = f.local_port; r.peer_port = f.peer_port;
+    r.role = (uint8_t)f.role; r.state = (uint8_t)k->state; r._pad = 0;
+    r.t_open = f.t_open; r.t_established = f.t_established; r.t_last_delivered = f.t_last_delivered; r.t_fin = f.t_fin;
+    r.bytes_delivered = f.bytes_delivered; r.packets_created = f.packets_created; r.bytes_created = f.bytes_created;
+    r.retransmitted = f.retransmitted; r.inet_dropped = f.inet_dropped; r.socket_dropped = f.socket_dropped;
+    r.router_dropped = f.router_dropped;
+    r.cwnd = k->cwnd; r.ssthresh = k->reno_ssthresh; r.srtt = k->srtt; r.rttvar = k->rttvar;
+    out[at] = r;
+}
+
 // a delivery from the round's input mailbox onto the host's heap (its packet
 // copied into the pool, its SACK list from the mailbox's arena)
 __device__ bool ingest_mail(L& c, int32_t s) {
@@ -3235,7 +3398,14 @@ enum WsSlot {
     kWsMnext, kWsCtl, kWsIpk, kWsNode, kWsTr, kWsTrs, kWsNextTime, kWsQlog, kWsNqlog, kWsProf, kWsProfRound,
     kWsAppSpec, kWsAppPeer, kWsDestCum, kWsHostClass, kWsIpAll, kWsBwu, kWsBwd, kWsProcPort, kWsPortNew, kWsXsend,
     kWsXrecv, kWsPmine, kWsPall, kWsXcnt, kWsGmine, kWsGall, kWsPcap, kWsNpcap, kWsPcapSlot, kWsHostHb, kWsSockOff, kWsDir, kWsIfq,
-    kWsProcOff, kWsSlots
+    kWsProcOff, kWsFlow, kWsFlowCnt, kWsFlowOff, kWsFlowOut, kWsSlots
+};
+// what the library allocates for a result: the public struct first (its size
+// is pinned), then the flow records shd_tcp_result_flows hands out
+struct TcpResultX {
+    shd_tcp_result pub;
+    shd_tcp_flow* flows;
+    uint64_t n_flows;
 };
 struct TcpWs {
     std::mutex mu;
@@ -3518,7 +3688,10 @@ static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, s
     std::vector<DHost> hh(nloc);
     std::vector<DProc> pp(P > 0 ? P : 1);
     std::vector<int32_t> hp, hpo, so;   // this engine's hosts: their processes and socket slots as ranges
-    shd_tcp_result* res = (shd_tcp_result*)calloc(1, sizeof(shd_tcp_result));
+    TcpResultX* resx = (TcpResultX*)calloc(1, sizeof(TcpResultX));
+    shd_tcp_result* res = &resx->pub;   // (the struct's first member: freed through it)
+    const bool flows_on = (m->options & SHD_TCP_OPT_FLOWS) != 0;
+    uint32_t* d_fcnt = nullptr; uint32_t* d_foff = nullptr;
     double* d_lat = nullptr; double* d_rel = nullptr;
     uint32_t* d_spec = nullptr; int32_t* d_apeer = nullptr; double* d_cum = nullptr; uint8_t* d_cls = nullptr;
     int32_t* d_hv = nullptr;
@@ -3591,6 +3764,7 @@ static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, s
         for (int32_t i = 0; i < nloc; i++) hb_min = std::min<uint64_t>(hb_min, m->host_heartbeat[h0 + i]);
     }
     g.tcp_bytes = m->tcp_bytes; g.trace = (trace & SHD_TCP_TRACE_STATUS) ? 1 : 0;
+    g.stat_on = g.trace;   // (| 2 with flow records, below)
     g.recv_buf = m->recv_buf; g.send_buf = m->send_buf; g.tcp_window = m->tcp_window;
     if (m->qdisc > 1) { free(res); return -22; }
     g.qdisc_rr = m->qdisc;
@@ -3707,6 +3881,19 @@ static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, s
         HCHECK(ws_alloc(ws, kWsDir, &g.dir, sizeof(DKey) * (ns + kDirPad)));
         HCHECK(hipMemset(g.dir, 0, sizeof(DKey) * (ns + kDirPad)));
         HCHECK(ws_alloc(ws, kWsIfq, &g.ifq, sizeof(int32_t) * ns));
+        if (flows_on) {   // a record beside every slot, and the gather's per-host counts and offsets
+            if (ws_alloc(ws, kWsFlow, &g.flow, sizeof(DFlow) * ns) != hipSuccess ||
+                ws_alloc(ws, kWsFlowCnt, &d_fcnt, sizeof(uint32_t) * (size_t)nloc) != hipSuccess ||
+                ws_alloc(ws, kWsFlowOff, &d_foff, sizeof(uint32_t) * ((size_t)nloc + 1)) != hipSuccess) {
+                (void)hipGetLastError();
+                fprintf(stderr, "shd_tcp_run: no device memory for the flow records of %zu socket slots\n", ns);
+                rc = -12;
+                goto done;
+            }
+            HCHECK(hipMemset(g.flow, 0, sizeof(DFlow) * ns));
+            g.flow_on = 1;
+            g.stat_on |= 2u;
+        }
         HCHECK(ws_alloc(ws, kWsProcOff, &d_hpo, sizeof(int32_t) * hpo.size()));
         HCHECK(hipMemcpy(d_hpo, hpo.data(), sizeof(int32_t) * hpo.size(), hipMemcpyHostToDevice));
         g.proc_off = d_hpo;
@@ -4021,6 +4208,33 @@ static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, s
     res->next_packet_id = (uint64_t*)calloc(nloc, sizeof(uint64_t));
     res->rng_probe = (uint32_t*)calloc(nloc, sizeof(uint32_t));
     res->rounds = rounds;
+    if (g.flow_on) {   // the records, compacted on the device in the result's order (k_tcp_flow_*)
+        const int32_t ns = so[nloc];
+        uint32_t nf = 0;
+        shd_tcp_flow* d_out = nullptr;
+        HCHECK(hipEventRecord(e0, st));
+        k_tcp_flow_count<<<(unsigned)((nloc + 255) / 256), 256, 0, st>>>(g, d_fcnt);
+        k_tcp_flow_scan<<<1, kFlowScan, 0, st>>>(d_fcnt, d_foff, nloc);
+        HCHECK(hipGetLastError());
+        HCHECK(hipMemcpyAsync(&nf, d_foff + nloc, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HCHECK(hipStreamSynchronize(st));
+        if (nf > (uint32_t)ns) { rc = -5; goto done; }   // (more records than slots: never)
+        resx->flows = (shd_tcp_flow*)malloc(sizeof(shd_tcp_flow) * (nf ? nf : 1));
+        resx->n_flows = nf;
+        if (nf) {
+            HCHECK(ws_alloc(ws, kWsFlowOut, &d_out, sizeof(shd_tcp_flow) * nf));
+            k_tcp_flow_write<<<(unsigned)((ns + 255) / 256), 256, 0, st>>>(g, d_foff, d_out, ns);
+            HCHECK(hipGetLastError());
+            HCHECK(hipMemcpyAsync(resx->flows, d_out, sizeof(shd_tcp_flow) * nf, hipMemcpyDeviceToHost, st));
+        }
+        HCHECK(hipEventRecord(e1, st));
+        HCHECK(hipEventSynchronize(e1));
+        if (getenv("SHD_TCP_FLOW_TIMING")) {   // the gather's device time (kernels and the copy back), for measurements
+            float fms = 0;
+            HCHECK(hipEventElapsedTime(&fms, e0, e1));
+            fprintf(stderr, "shd_tcp_run: %u flow records of %d slots gathered in %.3f ms\n", nf, ns, fms);
+        }
+    }
     if (any_pcap) {   // the capture hosts' records, hosts in index order (the slots' order)
         res->pcap_off = (uint64_t*)calloc((size_t)nloc + 1, sizeof(uint64_t));
         size_t tot = 0;
@@ -4206,5 +4420,14 @@ extern "C" void shd_tcp_result_free(shd_tcp_result* r) {
     free(r->n_heartbeats);
     free(r->pcap_records);
     free(r->pcap_off);
+    free(((TcpResultX*)r)->flows);   // (every result is allocated as a TcpResultX: tcp_run_impl)
     free(r);
+}
+
+extern "C" int shd_tcp_result_flows(const shd_tcp_result* r, const shd_tcp_flow** recs, uint64_t* n) {
+    if (!r || !recs || !n) return -22;
+    const TcpResultX* x = (const TcpResultX*)r;
+    *recs = x->n_flows ? x->flows : nullptr;   // (a run with the option and no connection: NULL and 0 as well)
+    *n = x->n_flows;
+    return 0;
 }

@@ -202,7 +202,7 @@ class TcpModel(C.Structure):
                 ("end_time", C.c_uint64), ("heartbeat_interval", C.c_uint64),
                 ("tcp_bytes", C.c_uint32), ("recv_buf", C.c_uint32), ("send_buf", C.c_uint32),
                 ("tcp_window", C.c_uint32), ("packets_per_host", C.c_uint32), ("qdisc", C.c_uint32),
-                ("_pad", C.c_uint32), ("path_cache", C.c_void_p),
+                ("options", C.c_uint32), ("path_cache", C.c_void_p),
                 ("proc_app", P(C.c_int32)), ("app_spec", P(C.c_uint32)), ("n_app_specs", C.c_int32),
                 ("udp_payload", C.c_uint32), ("app_peer", P(C.c_int32)), ("dest_cum", P(C.c_double)),
                 ("host_class", P(C.c_uint8)), ("n_classes", C.c_int32), ("_pad2", C.c_int32),
@@ -242,6 +242,33 @@ PCAP_IN, PCAP_OUT = 0, 1                               # shd_pcap_rec.dir
 PCAP_HEADERS_ONLY = 1                                  # shd_pcap_format / shd_pcap_write_host flags
 
 
+class TcpFlow(C.Structure):
+    """shd_tcp_flow (include/shdtcp.h): one TCP connection endpoint's record"""
+    _fields_ = [("host", C.c_int32), ("proc", C.c_int32), ("local_ip", C.c_uint32), ("peer_ip", C.c_uint32),
+                ("local_port", C.c_uint16), ("peer_port", C.c_uint16), ("role", C.c_uint8), ("state", C.c_uint8),
+                ("_pad", C.c_uint16),
+                ("t_open", C.c_uint64), ("t_established", C.c_uint64), ("t_last_delivered", C.c_uint64),
+                ("t_fin", C.c_uint64), ("bytes_delivered", C.c_uint64), ("packets_created", C.c_uint64),
+                ("bytes_created", C.c_uint64), ("retransmitted", C.c_uint64), ("inet_dropped", C.c_uint64),
+                ("socket_dropped", C.c_uint64), ("router_dropped", C.c_uint64),
+                ("cwnd", C.c_uint32), ("ssthresh", C.c_uint32), ("srtt", C.c_int32), ("rttvar", C.c_int32)]
+
+
+TCP_OPT_FLOWS = 1   # SHD_TCP_OPT_FLOWS (shd_tcp_model.options): a flow record per TCP connection endpoint
+# shd_tcp_flow as a structured dtype (the records shd_tcp_result_flows hands out); times in ns, 0: never
+TCP_FLOW_DTYPE = np.dtype([("host", "<i4"), ("proc", "<i4"), ("local_ip", "<u4"), ("peer_ip", "<u4"),
+                           ("local_port", "<u2"), ("peer_port", "<u2"), ("role", "u1"), ("state", "u1"),
+                           ("_pad", "<u2"),
+                           ("t_open", "<u8"), ("t_established", "<u8"), ("t_last_delivered", "<u8"), ("t_fin", "<u8"),
+                           ("bytes_delivered", "<u8"), ("packets_created", "<u8"), ("bytes_created", "<u8"),
+                           ("retransmitted", "<u8"), ("inet_dropped", "<u8"), ("socket_dropped", "<u8"),
+                           ("router_dropped", "<u8"),
+                           ("cwnd", "<u4"), ("ssthresh", "<u4"), ("srtt", "<i4"), ("rttvar", "<i4")])
+assert TCP_FLOW_DTYPE.itemsize == C.sizeof(TcpFlow) == 128
+TCP_STATE_NAMES = ("CLOSED", "LISTEN", "SYNSENT", "SYNRECEIVED", "ESTABLISHED", "FINWAIT1", "FINWAIT2", "CLOSING",
+                   "TIMEWAIT", "CLOSEWAIT", "LASTACK")   # shd_tcp_flow.state
+
+
 TCP_QUERY_DTYPE = np.dtype([("time", "<u8"), ("seq", "<u8"), ("host", "<u4"), ("src", "<u4"), ("index", "<u4"),
                             ("v_src", "<i4"), ("v_dst", "<i4"), ("_pad", "<u4")])   # shd_tcp_query
 
@@ -257,6 +284,7 @@ _SIGS = {
     "shd_tcp_run": (C.c_int, [P(TcpModel), C.c_int32, P(P(TcpResult))]),
     "shd_tcp_run_group": (C.c_int, [P(TcpModel), C.c_void_p, C.c_int32, P(P(TcpResult))]),
     "shd_tcp_result_free": (None, [P(TcpResult)]),
+    "shd_tcp_result_flows": (C.c_int, [P(TcpResult), P(P(TcpFlow)), P(C.c_uint64)]),
     "shd_tcp_keep_workspace": (None, [C.c_int32]),
     "shd_pcap_format": (C.c_size_t, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int32, C.c_void_p, C.c_size_t]),
     "shd_pcap_write_host": (C.c_int, [C.c_char_p, C.c_char_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32]),
@@ -476,6 +504,39 @@ def write_pcap_files(pcap_records, names, ips, directory=None, flags: int = 0) -
         base = "data/pcapdata/" if directory is None else os.fspath(directory)
         out.append(os.path.join(base, "%s-%s.pcap" % (names[h], ip_str(ips[h]))))
     return out
+
+
+def tcp_result_flows(res) -> np.ndarray:
+    """The flow records of a shd_tcp_result (pointer) as a TCP_FLOW_DTYPE array
+    of its own (shd_tcp_result_flows); empty when the model did not set
+    TCP_OPT_FLOWS."""
+    recs, n = P(TcpFlow)(), C.c_uint64()
+    check(lib().shd_tcp_result_flows(res, C.byref(recs), C.byref(n)), "shd_tcp_result_flows")
+    if not n.value:
+        return np.zeros(0, dtype=TCP_FLOW_DTYPE)
+    return np.frombuffer(C.string_at(recs, n.value * TCP_FLOW_DTYPE.itemsize), dtype=TCP_FLOW_DTYPE).copy()
+
+
+FLOW_CSV_FIELDS = ("host", "proc", "role", "local", "peer", "state", "t_open", "t_established", "t_last_delivered",
+                   "t_fin", "bytes_delivered", "packets_created", "bytes_created", "retransmitted", "inet_dropped",
+                   "socket_dropped", "router_dropped", "cwnd", "ssthresh", "srtt", "rttvar")
+
+
+def write_flows_csv(path, flows) -> int:
+    """Write flow records (TCP_FLOW_DTYPE, as tcp.run(..., flows=True) returns
+    them) as CSV: a header line (FLOW_CSV_FIELDS), then one line per record in
+    the records' order -- local and peer as a.b.c.d:port, state by name
+    (TCP_STATE_NAMES), times in ns (0: never).  Returns the number of records."""
+    f = np.asarray(flows, dtype=TCP_FLOW_DTYPE)
+    with open(path, "w") as out:
+        out.write(",".join(FLOW_CSV_FIELDS) + "\n")
+        for r in f:
+            st = int(r["state"])
+            row = dict(local="%s:%d" % (ip_str(r["local_ip"]), r["local_port"]),
+                       peer="%s:%d" % (ip_str(r["peer_ip"]), r["peer_port"]),
+                       state=TCP_STATE_NAMES[st] if st < len(TCP_STATE_NAMES) else str(st))
+            out.write(",".join(row[k] if k in row else str(int(r[k])) for k in FLOW_CSV_FIELDS) + "\n")
+    return len(f)
 
 
 def ip_str(ip: int) -> str:

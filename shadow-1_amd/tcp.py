@@ -100,7 +100,7 @@ def serial_first_queries(queries: np.ndarray):
 
 def run(model: S.ModelArrays, g: S.GraphArrays, ips, procs, peers, nbytes=20000, trace=True,
         recv_buf=RECV_BUF, send_buf=SEND_BUF, tcp_window=TCP_WINDOW, packets_per_host=0, guess_reversed=False,
-        node=False, qdisc=0, mode="device", udp=None, comm=None, pcap=None):
+        node=False, qdisc=0, mode="device", udp=None, comm=None, pcap=None, flows=False):
     """Run the TCP echo model on the GPU: procs = [(host, start ns)], peers =
     [-1 | server process]; ips: host-order uint32 per host.  Returns
     dict(lines=[(t, h, line)] in each host's order, next_event_id,
@@ -127,6 +127,14 @@ def run(model: S.ModelArrays, g: S.GraphArrays, ips, procs, peers, nbytes=20000,
     S.PCAP_DTYPE array in the interface's order} for the captured hosts the
     result covers, pcap_drains and pcap_ring_peak; S.write_pcap_files makes
     the files.
+    flows: a flow record for every TCP connection endpoint of the hosts the
+    result covers (shd_tcp_model.options & SHD_TCP_OPT_FLOWS), with or without
+    trace, on one engine and with comm: the result then has flows, a
+    S.TCP_FLOW_DTYPE array ordered by host, then by the socket's creation on
+    its host (a group's ranks concatenated in rank order are the one-engine
+    array); S.write_flows_csv writes them.  A client's completion time is
+    t_last_delivered once bytes_delivered == nbytes (equal to t_fin: the
+    client closes right after its last read).
     The model's bootstrap period (model.struct.bootstrap_end) and per-host
     heartbeat intervals (model.host_heartbeat) run as the reference's loop runs
     them (shd_tcp_model.bootstrap_end / host_heartbeat), on one engine and
@@ -141,7 +149,7 @@ def run(model: S.ModelArrays, g: S.GraphArrays, ips, procs, peers, nbytes=20000,
         try:
             out = _run_once(model, ips, procs, peers, None, None, hv.astype(np.int32), nbytes, trace, recv_buf,
                             send_buf, tcp_window, packets_per_host, node, qdisc, pc=pc, udp=udp, comm=comm,
-                            pcap=pcap)
+                            pcap=pcap, flows=flows)
         finally:
             pc.close()
         if out is not None:
@@ -153,7 +161,7 @@ def run(model: S.ModelArrays, g: S.GraphArrays, ips, procs, peers, nbytes=20000,
     V = lat.shape[0]
     for runs in range(1, 9):
         out = _run_once(model, ips, procs, peers, lat, rel, hvi, nbytes, trace, recv_buf, send_buf, tcp_window,
-                        packets_per_host, node, qdisc, udp=udp, comm=comm, pcap=pcap)
+                        packets_per_host, node, qdisc, udp=udp, comm=comm, pcap=pcap, flows=flows)
         order, pairs = serial_first_queries(out.pop("queries"))
         lat2, rel2 = resolve(g, att, order, pairs, V)
         ij = tuple(np.array([(a, b) for a, b in pairs] + [(b, a) for a, b in pairs], dtype=np.int64).T) \
@@ -173,12 +181,13 @@ def run(model: S.ModelArrays, g: S.GraphArrays, ips, procs, peers, nbytes=20000,
 
 
 def fill_model(model, ips, procs, peers, lat, rel, hvi, nbytes, recv_buf=RECV_BUF, send_buf=SEND_BUF,
-               tcp_window=TCP_WINDOW, packets_per_host=0, qdisc=0, pc=None, udp=None, pcap=None):
+               tcp_window=TCP_WINDOW, packets_per_host=0, qdisc=0, pc=None, udp=None, pcap=None, flows=False):
     """The shd_tcp_model of one run (no device needed): (TcpModel, the arrays
     its pointers refer to -- keep them alive as long as the struct is used).
     The model's bootstrap period and per-host heartbeat intervals
     (model.struct.bootstrap_end, model.host_heartbeat: <shadow bootstraptime>,
-    <host heartbeatfrequency>) go in as they are."""
+    <host heartbeatfrequency>) go in as they are.  flows: SHD_TCP_OPT_FLOWS in
+    the model's options."""
     m = model.struct
     H = int(m.n_hosts)
     keep = dict(ip=np.ascontiguousarray(ips, dtype=np.uint32), hv=np.ascontiguousarray(hvi, dtype=np.int32),
@@ -213,6 +222,7 @@ def fill_model(model, ips, procs, peers, lat, rel, hvi, nbytes, recv_buf=RECV_BU
     tm.tcp_window = tcp_window
     tm.packets_per_host = packets_per_host
     tm.qdisc = int(qdisc)   # --interface-qdisc: 0 fifo, 1 rr
+    tm.options = S.TCP_OPT_FLOWS if flows else 0
     if pc is not None:
         tm.path_cache = pc.ptr.value
     if udp is not None:
@@ -236,12 +246,12 @@ def fill_model(model, ips, procs, peers, lat, rel, hvi, nbytes, recv_buf=RECV_BU
 
 
 def _run_once(model, ips, procs, peers, lat, rel, hvi, nbytes, trace, recv_buf, send_buf, tcp_window,
-              packets_per_host, node=False, qdisc=0, pc=None, udp=None, comm=None, pcap=None):
+              packets_per_host, node=False, qdisc=0, pc=None, udp=None, comm=None, pcap=None, flows=False):
     """one shd_tcp_run on the given path tables, or with pc (sim.PathCache) on
     the cache itself (hvi: graph vertices then); None when that run's
     first-touch choices were contradicted (SHD_TCP_ERR_FIRST_TOUCH)"""
     tm, keep = fill_model(model, ips, procs, peers, lat, rel, hvi, nbytes, recv_buf, send_buf, tcp_window,
-                          packets_per_host, qdisc, pc=pc, udp=udp, pcap=pcap)
+                          packets_per_host, qdisc, pc=pc, udp=udp, pcap=pcap, flows=flows)
     res = C.POINTER(S.TcpResult)()
     bits = (S.TCP_TRACE_STATUS if trace else 0) | (S.TCP_TRACE_NODE if node else 0)
     if comm is not None:
@@ -274,6 +284,8 @@ def _run_once(model, ips, procs, peers, lat, rel, hvi, nbytes, trace, recv_buf, 
                    queries=np.frombuffer(C.string_at(r.queries, int(r.n_queries) * S.TCP_QUERY_DTYPE.itemsize),
                                          dtype=S.TCP_QUERY_DTYPE).copy() if r.n_queries else
                    np.zeros(0, dtype=S.TCP_QUERY_DTYPE))
+        if flows:
+            out["flows"] = S.tcp_result_flows(res)
         if pcap is not None:
             off = np.ctypeslib.as_array(r.pcap_off, shape=(HL + 1,)).copy()
             recs = np.frombuffer(C.string_at(r.pcap_records, int(off[-1]) * S.PCAP_DTYPE.itemsize),
