@@ -29,6 +29,17 @@
  * FIN and comes before the last delivery): 6 of the fixture's 97 completed
  * clients.
  *
+ * What a run says about its paths without tracing: with SHD_TCP_OPT_PATHS in
+ * shd_tcp_model.options, one path record (shd_tcp_path) for every ordered pair
+ * of vertices over which a host handed a packet to worker_sendPacket -- the
+ * packets and bytes the network carried and the ones it lost, TCP packets and
+ * the datagrams of a mixed model alike -- counted by the sending host's lane
+ * where INET_SENT / INET_DROPPED are raised, summed per pair in a table on the
+ * device and gathered at the end (shd_tcp_result_paths;
+ * tests/test_tcp_paths_gpu.py against tests/golden/ref_tcp_paths.json).  With
+ * path_cache the sends also go into the cache's packet counter
+ * (shd_pc_packet_count: the reference's Path.packetCount).
+ *
  * A host's shape comes from the model.  Its socket slots are the sockets it
  * can ever create -- a socket is not released in a TCP run: for each of its
  * server processes the listener and one child per client process that names
@@ -316,8 +327,41 @@ typedef struct shd_tcp_flow {
     int32_t srtt, rttvar;
 } shd_tcp_flow;
 
-/* shd_tcp_model.options */
-enum { SHD_TCP_OPT_FLOWS = 1 };
+/* One ordered vertex pair of a run with SHD_TCP_OPT_PATHS: what the hosts on
+ * v_src handed to worker_sendPacket for hosts on v_dst (worker.c:260-321),
+ * counted where the reference raises the packet's status, so every counted
+ * packet is one INET_SENT or INET_DROPPED [STATUS] line of a traced run
+ * (tests/tcp_path_expect.py).  A host's packets to its own address go through
+ * the loopback task (network_interface.c:548-555), never reach
+ * worker_sendPacket and are not counted; two hosts on one vertex give the
+ * pair (v, v).  Datagrams of shd_udp_app processes count like TCP packets. */
+typedef struct shd_tcp_path {
+    int32_t v_src, v_dst;          /* shd_tcp_model.host_vertex of the sending and of the destination host */
+    uint64_t packets_sent;         /* INET_SENT   (worker.c:290-306; counted where the status is raised,
+                                      also when the delivery would fall past end_time) */
+    uint64_t bytes_sent;           /* their payload (the line's bytes=) */
+    uint64_t control_sent;         /* those of them with payload 0 (never dropped, worker.c:288-290) */
+    uint64_t packets_dropped;      /* INET_DROPPED (worker.c:319) */
+    uint64_t bytes_dropped;
+    uint64_t t_first, t_last;      /* ns: first and last time worker_sendPacket handled a packet of the
+                                      pair, either outcome; a record exists only for a pair that saw one */
+} shd_tcp_path;
+
+/* shd_tcp_model.options: independent bits */
+enum { SHD_TCP_OPT_FLOWS = 1, SHD_TCP_OPT_PATHS = 2 };
+
+/* The most entries the device's pair table gets (SHD_TCP_OPT_PATHS; 64 bytes
+ * each: 256 MiB).  Its capacity is a power of two at least twice min(Vu^2, E +
+ * 2 Vd Vu) -- Vu the distinct host_vertex values, E the distinct ordered
+ * vertex pairs of the echo connections in both directions (a connection
+ * within one host has none), Vd the distinct vertices of hosts with a
+ * datagram process -- and at most this; SHD_TCP_PATH_SLOTS in the environment
+ * forces it (tests).  A model with more pairs in use than entries ends with
+ * SHD_TCP_ERR_PATHS.  SHD_TCP_PATH_TIMING in the environment (any value) makes
+ * a run with the option print, on stderr, the number of records, the table's
+ * capacity and the device time of the fold and the gather at its end
+ * (measurements: profiles/paths/ab.txt). */
+#define SHD_TCP_PATH_SLOTS_MAX (1u << 22)
 
 /* device bytes of one socket slot (its buffers, queues, SACK and retransmit
  * state at their fixed capacities) */
@@ -332,7 +376,9 @@ enum {
                                   than 16 sockets at once), or a listener held more than 8 children */
     SHD_TCP_ERR_MAILBOX = 16, SHD_TCP_ERR_TRACE = 32, SHD_TCP_ERR_SACK = 64, SHD_TCP_ERR_INTERNAL = 128,
     SHD_TCP_ERR_QLOG = 256, SHD_TCP_ERR_FIRST_TOUCH = 512,
-    SHD_TCP_ERR_PCAP = 1024   /* a capture ring filled between two drains (pcap_ring) */
+    SHD_TCP_ERR_PCAP = 1024,  /* a capture ring filled between two drains (pcap_ring) */
+    SHD_TCP_ERR_PATHS = 2048  /* the device's pair table had no free entry for a vertex pair (SHD_TCP_OPT_PATHS):
+                                 counts could not be placed, the path records are incomplete */
 };
 
 /* Run the model to end_time on the current HIP device (the reference's
@@ -360,6 +406,26 @@ void shd_tcp_result_free(shd_tcp_result* r);
  * rounds as before; a rerun from the start (first_touch_reruns) starts the
  * records again with it. */
 int shd_tcp_result_flows(const shd_tcp_result* r, const shd_tcp_flow** recs, uint64_t* n);
+
+/* The path records of the hosts this result covers (a result of shd_tcp_run /
+ * shd_tcp_run_group only): one for every ordered pair (v_src, v_dst) over
+ * which one of them handed a packet to worker_sendPacket, sorted by (v_src,
+ * v_dst).  A group's rank returns its own hosts' sends -- nothing is
+ * exchanged -- so the ranks' records summed per pair (t_first min, t_last
+ * max) are the one-engine records.  *recs NULL and *n 0 when the model did
+ * not set SHD_TCP_OPT_PATHS.  Owned by the result.  Returns 0, -22 for a NULL
+ * argument.  Without the option a run allocates nothing for them, launches
+ * nothing extra and runs the rounds as before; a rerun from the start
+ * (first_touch_reruns) starts the records again.
+ * With path_cache and the option, a run that ends without an error bit adds
+ * each pair's packets_sent to the cache's packet counter, keyed on the
+ * unordered attached pair as shd_pc_count_packet keys it: afterwards
+ * shd_pc_packet_count(pc, a, b) has grown by sent[a->b] + sent[b->a] (by
+ * sent[a->a] once for a pair on one vertex), the reference's
+ * Path.packetCount.  Once, after the last rerun; a group's rank adds its own
+ * hosts' sends to its own cache, as shd_eng_path_counts documents for engine
+ * groups. */
+int shd_tcp_result_paths(const shd_tcp_result* r, const shd_tcp_path** recs, uint64_t* n);
 
 /* The same model on a group of engines, one per process and GPU (shdgpu.h
  * shd_comm: RCCL, or the host-memory transport for several processes on one

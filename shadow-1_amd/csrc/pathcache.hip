@@ -2904,15 +2904,21 @@ done:
     return rc;
 }
 
+// n packets more over the unordered pair of attached indices (a, b): the
+// packet counter's one key format (shd_pc_count_packet; the TCP path's fold of
+// a run's path records, tcp.hip)
+__attribute__((visibility("hidden"))) void shd_pc_add_packets(shd_pc* pc, int32_t a, int32_t b, uint64_t n) {
+    auto* m = (std::unordered_map<uint64_t, uint64_t>*)pc->counts;
+    uint64_t key = ((uint64_t)(uint32_t)std::min(a, b) << 32) | (uint32_t)std::max(a, b);
+    (*m)[key] += n;
+}
+
 extern "C" int shd_pc_count_packet(shd_pc* pc, int32_t sv, int32_t dv) {
     double lat, rel;
     int rc = shd_pc_lookup(pc, sv, dv, &lat, &rel);
     if (rc) return rc;
     if (lat < 0) return SHD_OK;
-    auto* m = (std::unordered_map<uint64_t, uint64_t>*)pc->counts;
-    int32_t a = pc->h_att_index[sv], b = pc->h_att_index[dv];
-    uint64_t key = ((uint64_t)(uint32_t)std::min(a, b) << 32) | (uint32_t)std::max(a, b);
-    (*m)[key]++;
+    shd_pc_add_packets(pc, pc->h_att_index[sv], pc->h_att_index[dv], 1);
     return SHD_OK;
 }
 

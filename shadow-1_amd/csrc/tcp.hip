@@ -33,7 +33,11 @@
 // ranges of engine-wide arrays, so a hub host with dozens of sockets runs
 // beside hosts that hold one.  With SHD_TCP_OPT_FLOWS a flow record per TCP
 // connection endpoint is kept beside the socket slots (DFlow, flow_status)
-// and gathered by a kernel at the end (k_tcp_flow_*).
+// and gathered by a kernel at the end (k_tcp_flow_*).  With
+// SHD_TCP_OPT_PATHS the packets worker_send_packet sent and dropped are
+// counted per vertex pair: an accumulator beside each socket slot (DPath,
+// path_status), folded into a pair table in device memory (PEnt, path_add) and
+// compacted into shd_tcp_path records at the end (k_tcp_path_*).
 //
 // The work is branchy per-host control flow with a few events per host and
 // round: latency-bound by design ("TCP"); it shares nothing with
@@ -61,6 +65,7 @@
 // blocks of the largest size through host memory (synchronizes `s`)
 __attribute__((visibility("hidden"))) int shd_pc_fold_ranked(shd_pc* pc, const int32_t* old_rank,
                                                              const int32_t* old_self);
+__attribute__((visibility("hidden"))) void shd_pc_add_packets(shd_pc* pc, int32_t a, int32_t b, uint64_t n);
 __attribute__((visibility("hidden"))) int shd_comm_alltoallv_dev(shd_comm* c, const char* d_send,
                                                                  const size_t* send_off, const size_t* send_bytes,
                                                                  char* d_recv, const size_t* recv_off,
@@ -294,6 +299,28 @@ struct DFlow {
     uint32_t role;
 };
 static_assert(sizeof(DFlow) == 104, "a flow record beside each socket slot");
+// A socket slot's path accumulator (shd_tcp_model.options & SHD_TCP_OPT_PATHS):
+// Glob::pacc, one per slot beside the socket, not in it: what the slot's
+// packets added to the record of its current vertex pair (va, vb: Glob::hv's
+// indices) since the pair was last flushed.  Written by the slot's host's lane
+// only, with plain stores; sent + dropped != 0 says it holds something.
+struct DPath {
+    int32_t va, vb;
+    uint64_t packets_sent, bytes_sent, control_sent, packets_dropped, bytes_dropped;
+    uint64_t t_first, t_last;
+};
+static_assert(sizeof(DPath) == 64, "a path accumulator beside each socket slot");
+// An entry of the pair table (Glob::ptab, open addressing, linear probing):
+// key = va << 32 | vb claimed with a 64-bit compare-and-swap (kPathEmpty: free),
+// the counters added and the times folded with 64-bit atomics by whichever
+// lane flushes an accumulator of that pair.
+struct PEnt {
+    unsigned long long key;
+    unsigned long long packets_sent, bytes_sent, control_sent, packets_dropped, bytes_dropped;
+    unsigned long long t_first, t_last;
+};
+static_assert(sizeof(PEnt) == 64, "a pair table entry");
+constexpr unsigned long long kPathEmpty = ~0ull;
 
 // the round driver's device-side state (the host only reads it between batches)
 struct TCtl {
@@ -419,6 +446,14 @@ struct Glob {
     // what pkt_status tests: trace | flow_on << 1.
     DFlow* flow;
     uint32_t flow_on, stat_on;
+    // path records (SHD_TCP_OPT_PATHS): pacc [sock_off[nloc]], each slot's
+    // accumulator, and the pair table ptab [pt_mask + 1] (a power of two), both
+    // null without the option; *pt_full is set by an insert that found no free
+    // entry (SHD_TCP_ERR_PATHS).  path_on << 2 is stat_on's third bit.
+    DPath* pacc;
+    PEnt* ptab;
+    uint32_t* pt_full;
+    uint32_t pt_mask, path_on;
 };
 struct XSegHead { uint32_t n, nsack, err, _pad[13]; };   // 64 B, then xcap Mails, then xsack_cap SACK words
 static_assert(sizeof(XSegHead) == 64, "segment header");
@@ -659,18 +694,24 @@ __device__ bool sched_task(L& c, uint64_t delay, uint32_t kind, int32_t obj) {
 
 // ------------------------------------------------------------ packets and their lines
 // k: the socket raising the status, at the sites a flow record counts (flow_status)
+// and at worker_send_packet's two (path_status)
 __device__ void flow_status(L& c, const DSock* k, const DPkt* p, uint8_t st);
+__device__ __forceinline__ void path_status(L& c, const DSock* k, const DPkt* p, uint8_t st);
 __device__ void pkt_status(L& c, int32_t pi, uint8_t st, uint32_t trflags = 0,
                            const DSock* k = nullptr) {   // packet_addDeliveryStatus (packet.c:647-659)
     DPkt* p = PK(c, pi);
     DHost* H = c.H;
     if (st == S_SND_TCP_RETRANSMITTED) p->xflags |= kXRetx;   // packet_getDeliveryStatus's OR of every status
-    // one word says what a status feeds besides the packet: the lines (1) and
-    // the flow records (2).  A run with neither leaves here as it did when the
-    // word was Glob::trace alone: the records cost it no test of their own.
+    // one word says what a status feeds besides the packet: the lines (1),
+    // the flow records (2) and the path records (4).  A run with none leaves
+    // here as it did when the word was Glob::trace alone: the records cost it
+    // no test of their own.
     const uint32_t on = c.g->stat_on;
     if (__builtin_expect(!on, 1)) return;   // (the untraced run's path falls through)
     if (on & 2u) flow_status(c, k, p, st);
+    // (st is a constant where pkt_status is inlined: the count exists at worker_send_packet's two sites only,
+    // and every other function keeps the code it had)
+    if ((st == S_INET_SENT || st == S_INET_DROPPED) && (on & 4u)) path_status(c, k, p, st);
     if (!(on & 1u)) return;   // the list is read by the lines only
     if (p->nst < kSt) p->st[p->nst++] = st;
     else H->err |= SHD_TCP_ERR_TRACE;   // a line would lose statuses: fail, never truncate
@@ -782,6 +823,98 @@ __device__ void flow_status(L& c, const DSock* k, const DPkt* p, uint8_t st) {
         return;
     default:
         return;
+    }
+}
+
+// ------------------------------------------------------------ path records (shd_tcp_path)
+__device__ __forceinline__ uint32_t path_hash(unsigned long long key) {   // (splitmix64's finalizer)
+    key ^= key >> 30; key *= 0xbf58476d1ce4e5b9ull;
+    key ^= key >> 27; key *= 0x94d049bb133111ebull;
+    return (uint32_t)(key ^ (key >> 31));
+}
+// An accumulator's counts into its pair's table entry: the key claimed with a
+// compare-and-swap, then 64-bit atomic adds and min / max (many lanes may feed
+// one pair).  No free entry within the whole table: *pt_full is set and the
+// accumulator keeps what it held; the run ends with SHD_TCP_ERR_PATHS and its
+// records are incomplete -- an error, never a silently lost count.  (The fold
+// at the end of the run; the round kernel's own flush is path_flush.)
+__device__ bool path_add(const Glob& g, const DPath& a) {
+    const unsigned long long key = ((unsigned long long)(uint32_t)a.va << 32) | (uint32_t)a.vb;
+    uint32_t i = path_hash(key) & g.pt_mask;
+    for (uint32_t n = 0; n <= g.pt_mask; n++, i = (i + 1) & g.pt_mask) {
+        PEnt* e = &g.ptab[i];
+        unsigned long long cur = __hip_atomic_load(&e->key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (cur == kPathEmpty) cur = atomicCAS(&e->key, kPathEmpty, key);
+        if (cur != kPathEmpty && cur != key) continue;
+        if (a.packets_sent) atomicAdd(&e->packets_sent, (unsigned long long)a.packets_sent);
+        if (a.bytes_sent) atomicAdd(&e->bytes_sent, (unsigned long long)a.bytes_sent);
+        if (a.control_sent) atomicAdd(&e->control_sent, (unsigned long long)a.control_sent);
+        if (a.packets_dropped) atomicAdd(&e->packets_dropped, (unsigned long long)a.packets_dropped);
+        if (a.bytes_dropped) atomicAdd(&e->bytes_dropped, (unsigned long long)a.bytes_dropped);
+        atomicMin(&e->t_first, (unsigned long long)a.t_first);
+        atomicMax(&e->t_last, (unsigned long long)a.t_last);
+        return true;
+    }
+    atomicOr(g.pt_full, 1u);
+    return false;
+}
+// A re-keyed accumulator's counts into the table, inside the round kernel: as
+// path_add, but with one value in registers at a time (the key claimed by a
+// plain probe loop, each field read again right before its atomic), so that
+// the block behind the test at worker_send_packet's two sites needs no more
+// registers than if_send_packets has to spare there.  Inlined with path_add's
+// struct in hand, or as a call out of line, the same code cost the run
+// WITHOUT the option 0.7 to 1.2 % through if_send_packets's and k_tcp_round's
+// register allocation (profiles/paths/ab.txt).  A full table: *pt_full and the
+// host's SHD_TCP_ERR_PATHS; the accumulator starts again either way.
+__device__ __forceinline__ void path_flush(L& c, DPath* a) {
+    const Glob& g = *c.g;
+    const unsigned long long key = ((unsigned long long)(uint32_t)a->va << 32) | (uint32_t)a->vb;
+    uint32_t i = path_hash(key) & g.pt_mask, n = 0;
+    PEnt* e = nullptr;
+#pragma unroll 1
+    for (; n <= g.pt_mask; n++, i = (i + 1) & g.pt_mask) {
+        const unsigned long long cur = atomicCAS(&g.ptab[i].key, kPathEmpty, key);
+        if (cur == kPathEmpty || cur == key) { e = &g.ptab[i]; break; }
+    }
+    if (!e) {
+        atomicOr(g.pt_full, 1u);
+        c.H->err |= SHD_TCP_ERR_PATHS;
+    } else {
+        volatile DPath* v = a;
+        atomicAdd(&e->packets_sent, (unsigned long long)v->packets_sent);
+        atomicAdd(&e->bytes_sent, (unsigned long long)v->bytes_sent);
+        atomicAdd(&e->control_sent, (unsigned long long)v->control_sent);
+        atomicAdd(&e->packets_dropped, (unsigned long long)v->packets_dropped);
+        atomicAdd(&e->bytes_dropped, (unsigned long long)v->bytes_dropped);
+        atomicMin(&e->t_first, (unsigned long long)v->t_first);
+        atomicMax(&e->t_last, (unsigned long long)v->t_last);
+    }
+    a->packets_sent = a->bytes_sent = a->control_sent = a->packets_dropped = a->bytes_dropped = 0;
+}
+// The two count points: INET_SENT and INET_DROPPED (worker.c:290-306, 319),
+// raised by worker_send_packet with the sending socket k, whose cached path
+// (pc_ip, pc_va, pc_vb) it has just used or filled for this packet's
+// destination: the pair is the cache's.  (The cache is left unfilled only where
+// the run has already failed -- no such host, no route, an error bit of the
+// host -- and its results are invalid; nothing is counted then.)  A slot
+// whose pair changes (a datagram socket's next destination, a reused slot)
+// flushes what it held first.
+__device__ __forceinline__ void path_status(L& c, const DSock* k, const DPkt* p, uint8_t st) {
+    if (k->pc_ip != p->dip) return;
+    DPath* a = &c.g->pacc[sidx(c, k)];
+    const int32_t vb = k->pc_vb;
+    uint64_t held = a->packets_sent | a->packets_dropped;
+    if (held && a->vb != vb) { path_flush(c, a); held = 0; }
+    if (!held) { a->va = k->pc_va; a->vb = vb; a->t_first = c.now; }
+    a->t_last = c.now;
+    if (st == S_INET_SENT) {
+        a->packets_sent++;
+        a->bytes_sent += p->len;
+        a->control_sent += p->len == 0;
+    } else {
+        a->packets_dropped++;
+        a->bytes_dropped += p->len;
     }
 }
 
@@ -2022,7 +2155,7 @@ __device__ void worker_send_packet(L& c, int32_t pi, DSock* ks) {   // worker.c:
     const double chance = next_double(&c.H->rng);
     if (chance <= rel || p->len == 0 || c.now < c.g->boot_end) {
         const uint64_t t = c.now + (uint64_t)ceil(lat * (double)kMs);
-        pkt_status(c, pi, S_INET_SENT);
+        pkt_status(c, pi, S_INET_SENT, 0, ks);
         const uint64_t seq = c.H->ev_seq++;   // event_new_ (the delivery's ID)
         if (t >= c.g->end_time) return;
         if (d == c.gh) { c.H->err |= SHD_TCP_ERR_INTERNAL; return; }
@@ -3013,6 +3146,46 @@ __global__ void k_tcp_flow_write(Glob g, const uint32_t* __restrict__ off, shd_t
     out[at] = r;
 }
 
+// The run's path records at its end (SHD_TCP_OPT_PATHS): the table's entries
+// to kPathEmpty / zero before the run; after it every accumulator that holds
+// something folded into the table, one thread per socket slot, then the used
+// entries compacted into shd_tcp_path records -- a flag per entry, a prefix
+// over them (k_tcp_flow_scan), one thread per entry writing its record.  Only
+// the records go to the host, which names the vertices and sorts them.
+__global__ void k_tcp_path_init(PEnt* __restrict__ tab, uint32_t cap) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cap) return;
+    PEnt e;
+    e.key = kPathEmpty;
+    e.packets_sent = e.bytes_sent = e.control_sent = e.packets_dropped = e.bytes_dropped = 0;
+    e.t_first = ~0ull; e.t_last = 0;
+    tab[i] = e;
+}
+__global__ void k_tcp_path_fold(Glob g, int32_t ns) {   // one thread per socket slot
+    const int32_t s = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (s >= ns) return;
+    const DPath a = g.pacc[s];
+    if (!(a.packets_sent | a.packets_dropped)) return;
+    path_add(g, a);
+}
+__global__ void k_tcp_path_count(const PEnt* __restrict__ tab, uint32_t* __restrict__ cnt, uint32_t cap) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < cap) cnt[i] = tab[i].key != kPathEmpty;
+}
+__global__ void k_tcp_path_write(const PEnt* __restrict__ tab, const uint32_t* __restrict__ off,
+                                 shd_tcp_path* __restrict__ out, uint32_t cap) {   // one thread per entry
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cap) return;
+    const PEnt e = tab[i];
+    if (e.key == kPathEmpty) return;
+    shd_tcp_path r;
+    r.v_src = (int32_t)(e.key >> 32); r.v_dst = (int32_t)(uint32_t)e.key;   // (Glob::hv's indices: named on the host)
+    r.packets_sent = e.packets_sent; r.bytes_sent = e.bytes_sent; r.control_sent = e.control_sent;
+    r.packets_dropped = e.packets_dropped; r.bytes_dropped = e.bytes_dropped;
+    r.t_first = e.t_first; r.t_last = e.t_last;
+    out[off[i]] = r;
+}
+
 // a delivery from the round's input mailbox onto the host's heap (its packet
 // copied into the pool, its SACK list from the mailbox's arena)
 __device__ bool ingest_mail(L& c, int32_t s) {
@@ -3398,15 +3571,56 @@ enum WsSlot {
     kWsMnext, kWsCtl, kWsIpk, kWsNode, kWsTr, kWsTrs, kWsNextTime, kWsQlog, kWsNqlog, kWsProf, kWsProfRound,
     kWsAppSpec, kWsAppPeer, kWsDestCum, kWsHostClass, kWsIpAll, kWsBwu, kWsBwd, kWsProcPort, kWsPortNew, kWsXsend,
     kWsXrecv, kWsPmine, kWsPall, kWsXcnt, kWsGmine, kWsGall, kWsPcap, kWsNpcap, kWsPcapSlot, kWsHostHb, kWsSockOff, kWsDir, kWsIfq,
-    kWsProcOff, kWsFlow, kWsFlowCnt, kWsFlowOff, kWsFlowOut, kWsSlots
+    kWsProcOff, kWsFlow, kWsFlowCnt, kWsFlowOff, kWsFlowOut, kWsPacc, kWsPtab, kWsPtFull, kWsPtCnt, kWsPtOff,
+    kWsPtOut, kWsSlots
 };
 // what the library allocates for a result: the public struct first (its size
-// is pinned), then the flow records shd_tcp_result_flows hands out
+// is pinned), then the flow records shd_tcp_result_flows and the path records
+// shd_tcp_result_paths hand out
 struct TcpResultX {
     shd_tcp_result pub;
     shd_tcp_flow* flows;
     uint64_t n_flows;
+    shd_tcp_path* paths;
+    uint64_t n_paths;
 };
+// The pair table's capacity (shdtcp.h): a power of two at least twice the
+// most ordered vertex pairs the model's hosts can send over -- min(Vu^2, E + 2
+// Vd Vu): Vu distinct vertices, E the echo connections' distinct ordered
+// pairs in both directions (a connection within one host has none), Vd the
+// distinct vertices of hosts with a datagram process, whose destinations are
+// drawn -- at most SHD_TCP_PATH_SLOTS_MAX; SHD_TCP_PATH_SLOTS in the
+// environment forces it (rounded up to a power of two).
+static uint32_t tcp_path_slots(const shd_tcp_model* m, const std::vector<int32_t>& hvi) {
+    uint64_t want;
+    if (const char* e = getenv("SHD_TCP_PATH_SLOTS")) {
+        const long v = strtol(e, nullptr, 10);
+        want = v >= 1 ? (uint64_t)v : 1;
+    } else {
+        std::vector<int32_t> vu(hvi), vd;
+        std::sort(vu.begin(), vu.end());
+        vu.erase(std::unique(vu.begin(), vu.end()), vu.end());
+        std::vector<uint64_t> ep;
+        for (int32_t k = 0; k < m->n_procs; k++) {
+            const int32_t a = m->proc_host[k];
+            if (m->proc_app && m->proc_app[k] >= 0) { vd.push_back(hvi[a]); continue; }
+            if (m->proc_peer[k] < 0) continue;
+            const int32_t b = m->proc_host[m->proc_peer[k]];
+            if (a == b) continue;
+            ep.push_back(((uint64_t)(uint32_t)hvi[a] << 32) | (uint32_t)hvi[b]);
+            ep.push_back(((uint64_t)(uint32_t)hvi[b] << 32) | (uint32_t)hvi[a]);
+        }
+        std::sort(ep.begin(), ep.end());
+        ep.erase(std::unique(ep.begin(), ep.end()), ep.end());
+        std::sort(vd.begin(), vd.end());
+        vd.erase(std::unique(vd.begin(), vd.end()), vd.end());
+        const uint64_t nu = vu.size();
+        want = 2 * std::min<uint64_t>(nu * nu, ep.size() + 2 * (uint64_t)vd.size() * nu);
+    }
+    uint32_t cap = 1;
+    while (cap < want && cap < SHD_TCP_PATH_SLOTS_MAX) cap <<= 1;
+    return cap;
+}
 struct TcpWs {
     std::mutex mu;
     void* p[kWsSlots] = {};
@@ -3692,6 +3906,9 @@ static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, s
     shd_tcp_result* res = &resx->pub;   // (the struct's first member: freed through it)
     const bool flows_on = (m->options & SHD_TCP_OPT_FLOWS) != 0;
     uint32_t* d_fcnt = nullptr; uint32_t* d_foff = nullptr;
+    const bool paths_on = (m->options & SHD_TCP_OPT_PATHS) != 0;
+    uint32_t* d_pcnt = nullptr; uint32_t* d_poff = nullptr;
+    uint32_t pt_cap = 0;
     double* d_lat = nullptr; double* d_rel = nullptr;
     uint32_t* d_spec = nullptr; int32_t* d_apeer = nullptr; double* d_cum = nullptr; uint8_t* d_cls = nullptr;
     int32_t* d_hv = nullptr;
@@ -3893,6 +4110,27 @@ static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, s
             HCHECK(hipMemset(g.flow, 0, sizeof(DFlow) * ns));
             g.flow_on = 1;
             g.stat_on |= 2u;
+        }
+        if (paths_on) {   // an accumulator beside every slot, the pair table, and the gather's flags and offsets
+            pt_cap = tcp_path_slots(m, hvi);
+            if (ws_alloc(ws, kWsPacc, &g.pacc, sizeof(DPath) * ns) != hipSuccess ||
+                ws_alloc(ws, kWsPtab, &g.ptab, sizeof(PEnt) * (size_t)pt_cap) != hipSuccess ||
+                ws_alloc(ws, kWsPtFull, &g.pt_full, sizeof(uint32_t)) != hipSuccess ||
+                ws_alloc(ws, kWsPtCnt, &d_pcnt, sizeof(uint32_t) * (size_t)pt_cap) != hipSuccess ||
+                ws_alloc(ws, kWsPtOff, &d_poff, sizeof(uint32_t) * ((size_t)pt_cap + 1)) != hipSuccess) {
+                (void)hipGetLastError();
+                fprintf(stderr, "shd_tcp_run: no device memory for the path records (%zu socket slots, %u pairs)\n", ns,
+                        pt_cap);
+                rc = -12;
+                goto done;
+            }
+            HCHECK(hipMemset(g.pacc, 0, sizeof(DPath) * ns));
+            HCHECK(hipMemset(g.pt_full, 0, sizeof(uint32_t)));
+            k_tcp_path_init<<<(pt_cap + 255) / 256, 256>>>(g.ptab, pt_cap);
+            HCHECK(hipGetLastError());
+            g.pt_mask = pt_cap - 1;
+            g.path_on = 1;
+            g.stat_on |= 4u;
         }
         HCHECK(ws_alloc(ws, kWsProcOff, &d_hpo, sizeof(int32_t) * hpo.size()));
         HCHECK(hipMemcpy(d_hpo, hpo.data(), sizeof(int32_t) * hpo.size(), hipMemcpyHostToDevice));
@@ -4235,6 +4473,50 @@ static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, s
             fprintf(stderr, "shd_tcp_run: %u flow records of %d slots gathered in %.3f ms\n", nf, ns, fms);
         }
     }
+    if (g.path_on) {   // the accumulators folded, the table compacted (k_tcp_path_*), the records named and sorted
+        const int32_t ns = so[nloc];
+        uint32_t np = 0, full = 0;
+        shd_tcp_path* d_out = nullptr;
+        HCHECK(hipEventRecord(e0, st));
+        if (ns) k_tcp_path_fold<<<(unsigned)((ns + 255) / 256), 256, 0, st>>>(g, ns);
+        k_tcp_path_count<<<(pt_cap + 255) / 256, 256, 0, st>>>(g.ptab, d_pcnt, pt_cap);
+        k_tcp_flow_scan<<<1, kFlowScan, 0, st>>>(d_pcnt, d_poff, (int32_t)pt_cap);
+        HCHECK(hipGetLastError());
+        HCHECK(hipMemcpyAsync(&np, d_poff + pt_cap, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HCHECK(hipMemcpyAsync(&full, g.pt_full, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HCHECK(hipStreamSynchronize(st));
+        if (np > pt_cap) { rc = -5; goto done; }   // (more records than entries: never)
+        if (full) res->error |= SHD_TCP_ERR_PATHS;
+        resx->paths = (shd_tcp_path*)malloc(sizeof(shd_tcp_path) * (np ? np : 1));
+        if (!resx->paths) { rc = -12; goto done; }
+        resx->n_paths = np;
+        if (np) {
+            HCHECK(ws_alloc(ws, kWsPtOut, &d_out, sizeof(shd_tcp_path) * np));
+            k_tcp_path_write<<<(pt_cap + 255) / 256, 256, 0, st>>>(g.ptab, d_poff, d_out, pt_cap);
+            HCHECK(hipGetLastError());
+            HCHECK(hipMemcpyAsync(resx->paths, d_out, sizeof(shd_tcp_path) * np, hipMemcpyDeviceToHost, st));
+        }
+        HCHECK(hipEventRecord(e1, st));
+        HCHECK(hipEventSynchronize(e1));
+        if (getenv("SHD_TCP_PATH_TIMING")) {   // the fold's and gather's device time (with the copy back), for measurements
+            float pms = 0;
+            HCHECK(hipEventElapsedTime(&pms, e0, e1));
+            fprintf(stderr, "shd_tcp_run: %u path records from a table of %u entries (%d slots) folded and gathered in %.3f ms\n",
+                    np, pt_cap, ns, pms);
+        }
+        // the device's indices are Glob::hv's: the model's host_vertex on
+        // tables, the cache's attached indices otherwise -- named here
+        std::vector<int32_t> name(V, -1);
+        for (int32_t a = 0; a < H; a++) name[hvi[a]] = m->host_vertex[a];
+        for (uint32_t i = 0; i < np; i++) {
+            shd_tcp_path& r = resx->paths[i];
+            if (r.v_src < 0 || r.v_src >= V || r.v_dst < 0 || r.v_dst >= V) { rc = -5; goto done; }
+            r.v_src = name[r.v_src]; r.v_dst = name[r.v_dst];
+        }
+        std::sort(resx->paths, resx->paths + np, [](const shd_tcp_path& a, const shd_tcp_path& b) {
+            return a.v_src != b.v_src ? a.v_src < b.v_src : a.v_dst < b.v_dst;
+        });
+    }
     if (any_pcap) {   // the capture hosts' records, hosts in index order (the slots' order)
         res->pcap_off = (uint64_t*)calloc((size_t)nloc + 1, sizeof(uint64_t));
         size_t tot = 0;
@@ -4313,6 +4595,16 @@ static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, s
         res->deliveries += hout[i].deliveries;
         res->error |= hout[i].err;
         res->max_host_sockets = std::max<uint32_t>(res->max_host_sockets, (uint32_t)hout[i].nsock);
+    }
+    if (g.path_on && pc && !res->error) {
+        // Path.packetCount (topology_incrementPathPacketCounter, worker.c:296):
+        // the cache's own counter, keyed on the unordered attached pair as
+        // shd_pc_count_packet keys it, takes each pair's sends.  A run that a
+        // rerun follows ended with SHD_TCP_ERR_FIRST_TOUCH and folds nothing.
+        for (uint64_t i = 0; i < resx->n_paths; i++) {
+            const shd_tcp_path& r = resx->paths[i];
+            if (r.packets_sent) shd_pc_add_packets(pc, pc->h_att_index[r.v_src], pc->h_att_index[r.v_dst], r.packets_sent);
+        }
     }
     if (g.node) {
         res->node_k = g.node_k;
@@ -4421,6 +4713,7 @@ extern "C" void shd_tcp_result_free(shd_tcp_result* r) {
     free(r->pcap_records);
     free(r->pcap_off);
     free(((TcpResultX*)r)->flows);   // (every result is allocated as a TcpResultX: tcp_run_impl)
+    free(((TcpResultX*)r)->paths);
     free(r);
 }
 
@@ -4429,5 +4722,13 @@ extern "C" int shd_tcp_result_flows(const shd_tcp_result* r, const shd_tcp_flow*
     const TcpResultX* x = (const TcpResultX*)r;
     *recs = x->n_flows ? x->flows : nullptr;   // (a run with the option and no connection: NULL and 0 as well)
     *n = x->n_flows;
+    return 0;
+}
+
+extern "C" int shd_tcp_result_paths(const shd_tcp_result* r, const shd_tcp_path** recs, uint64_t* n) {
+    if (!r || !recs || !n) return -22;
+    const TcpResultX* x = (const TcpResultX*)r;
+    *recs = x->n_paths ? x->paths : nullptr;   // (a run with the option and no packet: NULL and 0 as well)
+    *n = x->n_paths;
     return 0;
 }

@@ -231,6 +231,7 @@ TCP_ERR_FIRST_TOUCH = 512                  # SHD_TCP_ERR_FIRST_TOUCH (include/sh
 TCP_SOCK_BYTES = 141888                     # SHD_TCP_SOCK_BYTES: device bytes of one socket slot
 TCP_ERR_SOCKETS = 8                        # SHD_TCP_ERR_SOCKETS: more sockets than the host's slots / a listener's 8 children
 TCP_ERR_PCAP = 1024                        # SHD_TCP_ERR_PCAP: a capture ring filled between two drains
+TCP_ERR_PATHS = 2048                       # SHD_TCP_ERR_PATHS: the device's pair table had no free entry
 
 # shd_pcap_rec (include/shdtcp.h): one captured packet; addresses and ports in host byte order
 PCAP_DTYPE = np.dtype([("time", "<u8"), ("src_ip", "<u4"), ("dst_ip", "<u4"), ("seq", "<u4"), ("ack", "<u4"),
@@ -269,6 +270,22 @@ TCP_STATE_NAMES = ("CLOSED", "LISTEN", "SYNSENT", "SYNRECEIVED", "ESTABLISHED", 
                    "TIMEWAIT", "CLOSEWAIT", "LASTACK")   # shd_tcp_flow.state
 
 
+class TcpPath(C.Structure):
+    """shd_tcp_path (include/shdtcp.h): one ordered vertex pair's traffic record"""
+    _fields_ = [("v_src", C.c_int32), ("v_dst", C.c_int32), ("packets_sent", C.c_uint64), ("bytes_sent", C.c_uint64),
+                ("control_sent", C.c_uint64), ("packets_dropped", C.c_uint64), ("bytes_dropped", C.c_uint64),
+                ("t_first", C.c_uint64), ("t_last", C.c_uint64)]
+
+
+TCP_OPT_PATHS = 2   # SHD_TCP_OPT_PATHS (shd_tcp_model.options): a traffic record per ordered vertex pair
+# shd_tcp_path as a structured dtype (the records shd_tcp_result_paths hands out); times in ns
+TCP_PATH_DTYPE = np.dtype([("v_src", "<i4"), ("v_dst", "<i4"), ("packets_sent", "<u8"), ("bytes_sent", "<u8"),
+                           ("control_sent", "<u8"), ("packets_dropped", "<u8"), ("bytes_dropped", "<u8"),
+                           ("t_first", "<u8"), ("t_last", "<u8")])
+assert TCP_PATH_DTYPE.itemsize == C.sizeof(TcpPath) == 64
+TCP_PATH_SUMS = ("packets_sent", "bytes_sent", "control_sent", "packets_dropped", "bytes_dropped")
+
+
 TCP_QUERY_DTYPE = np.dtype([("time", "<u8"), ("seq", "<u8"), ("host", "<u4"), ("src", "<u4"), ("index", "<u4"),
                             ("v_src", "<i4"), ("v_dst", "<i4"), ("_pad", "<u4")])   # shd_tcp_query
 
@@ -285,6 +302,7 @@ _SIGS = {
     "shd_tcp_run_group": (C.c_int, [P(TcpModel), C.c_void_p, C.c_int32, P(P(TcpResult))]),
     "shd_tcp_result_free": (None, [P(TcpResult)]),
     "shd_tcp_result_flows": (C.c_int, [P(TcpResult), P(P(TcpFlow)), P(C.c_uint64)]),
+    "shd_tcp_result_paths": (C.c_int, [P(TcpResult), P(P(TcpPath)), P(C.c_uint64)]),
     "shd_tcp_keep_workspace": (None, [C.c_int32]),
     "shd_pcap_format": (C.c_size_t, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int32, C.c_void_p, C.c_size_t]),
     "shd_pcap_write_host": (C.c_int, [C.c_char_p, C.c_char_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32]),
@@ -537,6 +555,52 @@ def write_flows_csv(path, flows) -> int:
                        state=TCP_STATE_NAMES[st] if st < len(TCP_STATE_NAMES) else str(st))
             out.write(",".join(row[k] if k in row else str(int(r[k])) for k in FLOW_CSV_FIELDS) + "\n")
     return len(f)
+
+
+def tcp_result_paths(res) -> np.ndarray:
+    """The path records of a shd_tcp_result (pointer) as a TCP_PATH_DTYPE array
+    of its own (shd_tcp_result_paths), sorted by (v_src, v_dst); empty when the
+    model did not set TCP_OPT_PATHS."""
+    recs, n = P(TcpPath)(), C.c_uint64()
+    check(lib().shd_tcp_result_paths(res, C.byref(recs), C.byref(n)), "shd_tcp_result_paths")
+    if not n.value:
+        return np.zeros(0, dtype=TCP_PATH_DTYPE)
+    return np.frombuffer(C.string_at(recs, n.value * TCP_PATH_DTYPE.itemsize), dtype=TCP_PATH_DTYPE).copy()
+
+
+def merge_tcp_paths(arrays) -> np.ndarray:
+    """The path records of a group's ranks (TCP_PATH_DTYPE arrays, each rank's
+    own hosts' sends) as the one-engine array: the records of one (v_src,
+    v_dst) summed, t_first the earliest, t_last the latest, sorted by the key."""
+    acc = {}
+    for a in arrays:
+        for r in np.asarray(a, dtype=TCP_PATH_DTYPE):
+            key = (int(r["v_src"]), int(r["v_dst"]))
+            have = acc.get(key)
+            if have is None:
+                acc[key] = {k: int(r[k]) for k in TCP_PATH_DTYPE.names}
+                continue
+            for k in TCP_PATH_SUMS:
+                have[k] += int(r[k])
+            have["t_first"] = min(have["t_first"], int(r["t_first"]))
+            have["t_last"] = max(have["t_last"], int(r["t_last"]))
+    out = np.zeros(len(acc), dtype=TCP_PATH_DTYPE)
+    for i, key in enumerate(sorted(acc)):
+        for k, v in acc[key].items():
+            out[k][i] = v
+    return out
+
+
+def write_paths_csv(path, recs) -> int:
+    """Write path records (TCP_PATH_DTYPE, as tcp.run(..., paths=True) returns
+    them) as CSV: a header line (the dtype's field names), then one line per
+    record in the records' order; times in ns.  Returns the number of records."""
+    a = np.asarray(recs, dtype=TCP_PATH_DTYPE)
+    with open(path, "w") as out:
+        out.write(",".join(TCP_PATH_DTYPE.names) + "\n")
+        for r in a:
+            out.write(",".join(str(int(r[k])) for k in TCP_PATH_DTYPE.names) + "\n")
+    return len(a)
 
 
 def ip_str(ip: int) -> str:

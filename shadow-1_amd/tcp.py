@@ -100,7 +100,7 @@ def serial_first_queries(queries: np.ndarray):
 
 def run(model: S.ModelArrays, g: S.GraphArrays, ips, procs, peers, nbytes=20000, trace=True,
         recv_buf=RECV_BUF, send_buf=SEND_BUF, tcp_window=TCP_WINDOW, packets_per_host=0, guess_reversed=False,
-        node=False, qdisc=0, mode="device", udp=None, comm=None, pcap=None, flows=False):
+        node=False, qdisc=0, mode="device", udp=None, comm=None, pcap=None, flows=False, paths=False):
     """Run the TCP echo model on the GPU: procs = [(host, start ns)], peers =
     [-1 | server process]; ips: host-order uint32 per host.  Returns
     dict(lines=[(t, h, line)] in each host's order, next_event_id,
@@ -135,6 +135,13 @@ def run(model: S.ModelArrays, g: S.GraphArrays, ips, procs, peers, nbytes=20000,
     array); S.write_flows_csv writes them.  A client's completion time is
     t_last_delivered once bytes_delivered == nbytes (equal to t_fin: the
     client closes right after its last read).
+    paths: a traffic record for every ordered vertex pair over which a host
+    the result covers sent (shd_tcp_model.options & SHD_TCP_OPT_PATHS), with
+    or without trace: the result then has paths, a S.TCP_PATH_DTYPE array
+    sorted by (v_src, v_dst), both graph vertex ids in either mode (on tables
+    the table's indices are mapped back), so the two modes' arrays are equal
+    byte for byte.  With comm the array is this rank's own hosts' sends;
+    S.merge_tcp_paths sums the ranks'; S.write_paths_csv writes them.
     The model's bootstrap period (model.struct.bootstrap_end) and per-host
     heartbeat intervals (model.host_heartbeat) run as the reference's loop runs
     them (shd_tcp_model.bootstrap_end / host_heartbeat), on one engine and
@@ -149,7 +156,7 @@ def run(model: S.ModelArrays, g: S.GraphArrays, ips, procs, peers, nbytes=20000,
         try:
             out = _run_once(model, ips, procs, peers, None, None, hv.astype(np.int32), nbytes, trace, recv_buf,
                             send_buf, tcp_window, packets_per_host, node, qdisc, pc=pc, udp=udp, comm=comm,
-                            pcap=pcap, flows=flows)
+                            pcap=pcap, flows=flows, paths=paths)
         finally:
             pc.close()
         if out is not None:
@@ -161,7 +168,12 @@ def run(model: S.ModelArrays, g: S.GraphArrays, ips, procs, peers, nbytes=20000,
     V = lat.shape[0]
     for runs in range(1, 9):
         out = _run_once(model, ips, procs, peers, lat, rel, hvi, nbytes, trace, recv_buf, send_buf, tcp_window,
-                        packets_per_host, node, qdisc, udp=udp, comm=comm, pcap=pcap, flows=flows)
+                        packets_per_host, node, qdisc, udp=udp, comm=comm, pcap=pcap, flows=flows, paths=paths)
+        if paths:   # the table's indices back to graph vertices
+            p = out["paths"]
+            names = np.asarray(att, dtype=np.int32)
+            p["v_src"], p["v_dst"] = names[p["v_src"]], names[p["v_dst"]]
+            out["paths"] = p[np.lexsort((p["v_dst"], p["v_src"]))]
         order, pairs = serial_first_queries(out.pop("queries"))
         lat2, rel2 = resolve(g, att, order, pairs, V)
         ij = tuple(np.array([(a, b) for a, b in pairs] + [(b, a) for a, b in pairs], dtype=np.int64).T) \
@@ -181,13 +193,14 @@ def run(model: S.ModelArrays, g: S.GraphArrays, ips, procs, peers, nbytes=20000,
 
 
 def fill_model(model, ips, procs, peers, lat, rel, hvi, nbytes, recv_buf=RECV_BUF, send_buf=SEND_BUF,
-               tcp_window=TCP_WINDOW, packets_per_host=0, qdisc=0, pc=None, udp=None, pcap=None, flows=False):
+               tcp_window=TCP_WINDOW, packets_per_host=0, qdisc=0, pc=None, udp=None, pcap=None, flows=False,
+               paths=False):
     """The shd_tcp_model of one run (no device needed): (TcpModel, the arrays
     its pointers refer to -- keep them alive as long as the struct is used).
     The model's bootstrap period and per-host heartbeat intervals
     (model.struct.bootstrap_end, model.host_heartbeat: <shadow bootstraptime>,
     <host heartbeatfrequency>) go in as they are.  flows: SHD_TCP_OPT_FLOWS in
-    the model's options."""
+    the model's options; paths: SHD_TCP_OPT_PATHS."""
     m = model.struct
     H = int(m.n_hosts)
     keep = dict(ip=np.ascontiguousarray(ips, dtype=np.uint32), hv=np.ascontiguousarray(hvi, dtype=np.int32),
@@ -222,7 +235,7 @@ def fill_model(model, ips, procs, peers, lat, rel, hvi, nbytes, recv_buf=RECV_BU
     tm.tcp_window = tcp_window
     tm.packets_per_host = packets_per_host
     tm.qdisc = int(qdisc)   # --interface-qdisc: 0 fifo, 1 rr
-    tm.options = S.TCP_OPT_FLOWS if flows else 0
+    tm.options = (S.TCP_OPT_FLOWS if flows else 0) | (S.TCP_OPT_PATHS if paths else 0)
     if pc is not None:
         tm.path_cache = pc.ptr.value
     if udp is not None:
@@ -246,12 +259,13 @@ def fill_model(model, ips, procs, peers, lat, rel, hvi, nbytes, recv_buf=RECV_BU
 
 
 def _run_once(model, ips, procs, peers, lat, rel, hvi, nbytes, trace, recv_buf, send_buf, tcp_window,
-              packets_per_host, node=False, qdisc=0, pc=None, udp=None, comm=None, pcap=None, flows=False):
+              packets_per_host, node=False, qdisc=0, pc=None, udp=None, comm=None, pcap=None, flows=False,
+              paths=False):
     """one shd_tcp_run on the given path tables, or with pc (sim.PathCache) on
     the cache itself (hvi: graph vertices then); None when that run's
     first-touch choices were contradicted (SHD_TCP_ERR_FIRST_TOUCH)"""
     tm, keep = fill_model(model, ips, procs, peers, lat, rel, hvi, nbytes, recv_buf, send_buf, tcp_window,
-                          packets_per_host, qdisc, pc=pc, udp=udp, pcap=pcap, flows=flows)
+                          packets_per_host, qdisc, pc=pc, udp=udp, pcap=pcap, flows=flows, paths=paths)
     res = C.POINTER(S.TcpResult)()
     bits = (S.TCP_TRACE_STATUS if trace else 0) | (S.TCP_TRACE_NODE if node else 0)
     if comm is not None:
@@ -286,6 +300,8 @@ def _run_once(model, ips, procs, peers, lat, rel, hvi, nbytes, trace, recv_buf, 
                    np.zeros(0, dtype=S.TCP_QUERY_DTYPE))
         if flows:
             out["flows"] = S.tcp_result_flows(res)
+        if paths:
+            out["paths"] = S.tcp_result_paths(res)
         if pcap is not None:
             off = np.ctypeslib.as_array(r.pcap_off, shape=(HL + 1,)).copy()
             recs = np.frombuffer(C.string_at(r.pcap_records, int(off[-1]) * S.PCAP_DTYPE.itemsize),
