@@ -9,7 +9,8 @@ Stamps (100 MHz wall clock; every stamp first drains the wave's memory ops):
 0 round start, 1 hand-off words read (idle test; k_round_sp: the scan and compaction), 2 bins + inbox merged and
 sorted, 3 last flush starts, 4 event loop + flushes done, 5 close done
 (bin resets, last deliveries), 6 share published (drained), 7 every share of
-the round seen.  Printed relative to the round's earliest start: mean over
+the round seen; k_round_ps also 21 the last flush's claims back and its stores
+issued, 22 the gather's poll passes.  Printed relative to the round's earliest start: mean over
 rounds of the mean and the max over blocks; and the phase durations.
 """
 import ctypes as C
@@ -101,6 +102,9 @@ def main():
     for k in range(8):
         v = rows[:, :, k]
         print(f"  {k} {names[k]:12s} mean {np.nanmean(v):6.2f}  max {np.nanmean(np.nanmax(v, axis=1)):6.2f}")
+    # block 0 (the summary's atomics, ps_fresh, the counts' plane in its polls) against the mean block
+    print("  block 0: " + ", ".join(f"{names[k]} {np.nanmean(rows[:, 0, k]):.2f} (mean {np.nanmean(rows[:, :, k]):.2f})"
+                                    for k in (0, 5, 6, 7)))
     # the last flush's resolve loop (stamps 12, 13), in blocks that flushed
     fl = []
     for r in range(64):
@@ -112,6 +116,27 @@ def main():
     if fl:
         print(f"  last flush resolve: starts mean {np.mean([a.mean() for a, _ in fl]):.2f} us, lasts mean "
               f"{np.mean([b.mean() for _, b in fl]):.2f} / max {np.mean([b.max() for _, b in fl]):.2f} us")
+    # k_round_ps's tail: the last flush's claims back and its stores issued (21), the publish drain
+    # (close done 5 -> published 6), the gather's poll passes (22)
+    cr, dr, npo = [], [], []
+    for r in range(64):
+        x = t_all[r]
+        t0 = x[:, 0].min()
+        ok = (t0 > 0) & (x[:, 21] >= x[:, 4]) & (x[:, 4] >= t0) & (x[:, 5] >= x[:, 21]) & (x[:, 6] >= x[:, 5])
+        if ok.any():
+            cr.append(((x[ok, 21] - t0) / 100.0, (x[ok, 21] - x[ok, 4]) / 100.0, (x[ok, 5] - x[ok, 21]) / 100.0))
+            dr.append((x[ok, 6] - x[ok, 5]) / 100.0)
+        ok = (t0 > 0) & (x[:, 7] >= t0) & (x[:, 22] > 0) & (x[:, 22] < 100000)
+        if ok.any():
+            npo.append(x[ok, 22])
+    if cr:
+        print(f"  claims back, stores issued: at mean {np.mean([a.mean() for a, _, _ in cr]):.2f} / max "
+              f"{np.mean([a.max() for a, _, _ in cr]):.2f} us; loop done -> there {np.mean([b.mean() for _, b, _ in cr]):.2f} us, "
+              f"there -> close done {np.mean([c.mean() for _, _, c in cr]):.2f} us; publish drain (close done -> published) "
+              f"mean {np.mean([d.mean() for d in dr]):.2f} / max {np.mean([d.max() for d in dr]):.2f} us")
+    if npo:
+        print(f"  gather poll passes per block and round: mean {np.mean([a.mean() for a in npo]):.2f}, max "
+              f"{np.mean([a.max() for a in npo]):.2f}")
     # the event loop: iterations (16), flushes (17), active lanes (18) per block and round, and
     # how the loop's length (stamp 2 -> 4) follows them
     it, nfl, nact, dur, seg = [], [], [], [], []

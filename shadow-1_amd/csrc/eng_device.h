@@ -800,6 +800,10 @@ __device__ __forceinline__ void st16_sys(void* p, uint4 v) {
 // the calendar-less part of a delivery: the inbox of a local destination
 // (merged into its heap next round), else the peer's all-to-all block or the
 // remote outbox
+// (XCH false: a kernel no group ever launches -- k_round_ps, k_round_sp: their
+// parameters are the engine's own, without a group's blocks (launch_batch_ps)
+// -- is compiled without the two exchange branches and owner_of's divisions)
+template <bool XCH = true>
 __device__ void emit_nocal(const DParams& P, HostCtx& c, const shd_event& e) {
     const int32_t dl = (int32_t)e.dst - P.h0;
     if (dl >= 0 && dl < P.nloc) {
@@ -808,7 +812,7 @@ __device__ void emit_nocal(const DParams& P, HostCtx& c, const shd_event& e) {
         if (slot >= P.inbox_cap) { c.err |= SHD_ERR_INBOX_OVERFLOW; return; }
         ev_st_sc1(&P.inbox[c.np][(size_t)dl * P.inbox_cap + slot], e);
     } else {
-        if (P.xcnt) {   // fused peer-to-peer rounds: into the region of the destination's block
+        if (XCH && P.xcnt) {   // fused peer-to-peer rounds: into the region of the destination's block
             const int32_t peer = owner_of(P, e.dst);
             const uint32_t hp0 = (uint32_t)(((uint64_t)P.H * (uint64_t)peer) / (uint64_t)P.xworld);
             const uint32_t blk = (e.dst - hp0) / (uint32_t)P.hpw;
@@ -824,7 +828,7 @@ __device__ void emit_nocal(const DParams& P, HostCtx& c, const shd_event& e) {
                 return;
             }
             // region full: spill (as a full block below)
-        } else if (P.xsend) {   // exchange mode: straight into the peer's all-to-all block
+        } else if (XCH && P.xsend) {   // exchange mode: straight into the peer's all-to-all block
             const int32_t peer = owner_of(P, e.dst);
             const uint32_t s = atomicAdd(&P.xcount[peer], 1u);
             if (s < P.xcap) {
@@ -1185,7 +1189,8 @@ __device__ void worker_send_deferred(const DParams& P, HostCtx& c, uint32_t rv, 
 // sends in order (event IDs, counters, traces, first-touch logs, LDS only);
 // then record-parallel deliveries (one round trip for the calendar claims).
 // a delivery of the round's last flush whose calendar claim is in flight:
-// its store waits until the round's closing work is issued (flush_finish)
+// its store follows once the per-host walk is done (flush_finish, ahead of
+// the round's closing work)
 struct PendDel {
     uint64_t bi;     // bin index
     uint32_t slot;   // claimed slot (kind 1)
@@ -1206,7 +1211,7 @@ __device__ __forceinline__ int32_t closed_dest(const DParams& P, uint32_t r) {
     return d;
 }
 
-template <bool PS = false>
+template <bool PS = false, bool XCH = true>
 __device__ __forceinline__ void flush_wave(const DParams& P, HostCtx& c, bool defer, PendDel& pd) {
     pd.kind = 0;
     const uint32_t lane = threadIdx.x;
@@ -1265,8 +1270,8 @@ __device__ __forceinline__ void flush_wave(const DParams& P, HostCtx& c, bool de
         e.kind = (pass ? 1u : 0u) | (pv.log ? 2u : 0u) | (pv.resolved ? 4u : 0u);
         s_res[r] = e;
         // the round's last flush (one batch: record r is lane r's): the
-        // calendar claim goes out now, under the per-host walk and the
-        // round's closing work; the store follows in flush_finish
+        // calendar claim goes out now, under the per-host walk; the store
+        // follows in flush_finish
         if (one && pass && pv.resolved && e.time < c.k.end_time) {
             const int32_t dl = (int32_t)dst - P.h0;
             const uint64_t bb = e.time >> P.bin_shift;
@@ -1336,8 +1341,9 @@ __device__ __forceinline__ void flush_wave(const DParams& P, HostCtx& c, bool de
     TIMP(14);
 #endif
     // deliveries: calendar claims for 64 events at a time, then the stores.
-    // The round's last flush (one batch) only issues the claims; the stores
-    // follow the round's closing work, which hides the claims' round trip.
+    // The round's last flush (one batch) only issues the claims, in the
+    // resolve loop: the per-host walk hides their round trip, and the stores
+    // go out before the round's closing work, which hides their write-through.
     if (one) {   // claims already issued in the resolve loop
         c.err |= err;
         return;   // s_res[lane] stays for flush_finish
@@ -1360,13 +1366,14 @@ __device__ __forceinline__ void flush_wave(const DParams& P, HostCtx& c, bool de
                 continue;
             }
         }
-        emit_nocal(P, c, e);
+        emit_nocal<XCH>(P, c, e);
     }
     c.err |= err;
     __syncthreads();   // s_res is reused by the next flush
 }
 
 // the stores of the round's last flush (after its claims returned)
+template <bool XCH = true>
 __device__ __forceinline__ void flush_finish(const DParams& P, HostCtx& c, const PendDel& pd) {
     if (pd.kind == 0) return;
     const shd_event e = s_res[threadIdx.x];
@@ -1378,7 +1385,7 @@ __device__ __forceinline__ void flush_finish(const DParams& P, HostCtx& c, const
         if (pd.near) note_dirty(dl);
         return;
     }
-    emit_nocal(P, c, e);
+    emit_nocal<XCH>(P, c, e);
 }
 
 // _networkinterface_sendPackets (network_interface.c:519-579), FIFO qdisc.

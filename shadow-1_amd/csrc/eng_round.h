@@ -1244,12 +1244,12 @@ __device__ __forceinline__ uint64_t cal_lower_bound_sp(const DParams& P, const u
 
 // The round's event loop (as round_body's: per-lane state 0 needs its next
 // event, 1 runs one, 2 waits for a flush, 3 done; wave-uniform exits only)
-// and its close: the lane's next time (an idle lane's from its timers and
-// bitmap), the last flush's stores.  PF: clr (bit j: ring position clr_p + j)
+// and its close: the last flush's stores, then the lane's next time (an idle
+// lane's from its timers and bitmap).  PF: clr (bit j: ring position clr_p + j)
 // is cleared from w first (bins the prologue reset, when w was loaded in
 // parallel), and the next window's bins are loaded between the loop and the
 // close, into *pb; *span: the bitmap's span from we's bin on, for the next round.
-template <bool PF>
+template <bool PF, bool XCH = true>
 __device__ __forceinline__ void ps_loop_close(const DParams& P, HostCtx& c, bool active, bool has, const PsRsrc& R,
                                               uint32_t lb, uint64_t we, uint32_t (&w)[kNBW], uint32_t clr_p,
                                               uint32_t clr, uint64_t& next, PfBins* pb, uint64_t* span) {
@@ -1336,7 +1336,7 @@ __device__ __forceinline__ void ps_loop_close(const DParams& P, HostCtx& c, bool
             n_fl++;
             ta = wall_clock64();
 #endif
-            flush_wave<true>(P, c, last, pd);
+            flush_wave<true, XCH>(P, c, last, pd);
 #ifdef SHD_TIMING_LIGHT
             if (!last) t_fl += wall_clock64() - ta;
 #endif
@@ -1355,6 +1355,15 @@ __device__ __forceinline__ void ps_loop_close(const DParams& P, HostCtx& c, bool
     TIMVP(11, t_q[0]);   // of 8: take_next
     TIMVP(15, t_q[1]);   //       begin_event
     TIMVP(19, t_q[2]);   //       the fused notification (the rest: the fused refill, the loop's own)
+#endif
+    // the last flush's stores first: they wait for the calendar claims alone
+    // (issued in the resolve loop, nothing behind them in the queue yet), and
+    // their write-through runs under the close instead of in front of the
+    // share's drain.  A delivery into a bin loaded ahead below is noted here,
+    // before ps_noted reads the list.
+    flush_finish<XCH>(P, c, pd);
+#ifdef SHD_TIMING_LIGHT
+    if (PF) TIMP(21);   // the claims are back, the last flush's stores issued (k_round_sp: 20, 21 are its own)
 #endif
     uint64_t sp = 0;
     if (PF) {
@@ -1378,18 +1387,17 @@ __device__ __forceinline__ void ps_loop_close(const DParams& P, HostCtx& c, bool
             next = cb < next ? cb : next;
         }
     }
-    flush_finish(P, c, pd);
     TIMP(5);
 }
 
 // k_round_sp's round of an active host (ps_prologue + ps_loop_close)
-template <bool SP>
+template <bool SP, bool XCH = true>
 __device__ __forceinline__ void ps_round_body(const DParams& P, HostCtx& c, bool active, uint32_t lb, const PsRsrc& R,
                                               uint64_t ws, uint64_t we, int parity, uint32_t nin,
                                               uint32_t (&w)[kNBW], uint32_t wbits, uint64_t& next,
                                               const SpIn* sp = nullptr) {
     ps_prologue<SP>(P, c, active, lb, R, ws, we, parity, nin, w, wbits, sp);
-    ps_loop_close<false>(P, c, active, active, R, lb, we, w, 0u, 0u, next, nullptr, nullptr);
+    ps_loop_close<false, XCH>(P, c, active, active, R, lb, we, w, 0u, 0u, next, nullptr, nullptr);
 }
 
 // The shares' granules are stored in three planes (round 6): granule g of slot
@@ -1431,15 +1439,16 @@ __device__ __forceinline__ uint4 ps_noted(bool pf) {
 // carry `tag`, folding them; block 0 also folds the counts.  DIRTY: the noted
 // destinations too -- bit k of `dmask`: host hb + k of this block was named,
 // `dall`: some block noted more than it could name.  False on timeout
+// (npass: the poll passes made, for the timing build's stamps)
 template <bool DIRTY, int K = 4>
 __device__ __forceinline__ bool ps_gather(__amdgpu_buffer_rsrc_t rs, uint32_t nsl, uint32_t base, uint32_t nblk, uint32_t tag,
                                           bool counts,
                           uint64_t ticks, uint64_t& next, uint32_t& flags, uint32_t& nev, uint32_t& npkt,
                           uint32_t& nact, uint32_t hb = 0, uint32_t hpw = 0, uint64_t* dmask = nullptr,
-                          bool* dall = nullptr) {
+                          bool* dall = nullptr, uint32_t* npass = nullptr) {
     next = kInf; flags = 0; nev = 0; npkt = 0; nact = 0;
     uint64_t dm = 0;
-    uint32_t da = 0;
+    uint32_t da = 0, pass = 0;
     const unsigned long long t0 = wall_clock64();
     for (uint32_t c0 = 0; c0 < nblk; c0 += 64u * K) {
         uint32_t need = 0;
@@ -1479,10 +1488,12 @@ __device__ __forceinline__ bool ps_gather(__amdgpu_buffer_rsrc_t rs, uint32_t ns
                 }
                 need &= ~(1u << k);
             }
+            pass++;
             if (__ballot(need != 0) == 0) break;
             if (wall_clock64() - t0 > ticks) return false;
         }
     }
+    if (npass) *npass = pass;
     // the folds, wave-uniform (scalar registers); the counts only where they were loaded
     next = wave_min_u64(next);
     flags = wave_or_u32(flags);
@@ -1516,8 +1527,8 @@ __device__ __forceinline__ void ps_fresh(DevSummary* s) {
 // ends: a delivery made in round i lands at or after we_i + W, so only the
 // sends with a latency below ~3 W can reach the bins [b(we_i), b(we_i) + 3)
 // after the receiver has read them.  So each block loads those bins of its
-// hosts between its last flush and its close (the loads overlap the flush's
-// claims and the close's stores, and land before the share's drain), stages
+// hosts between its last flush's stores and its close (the loads overlap the
+// stores' write-through and the close, and land before the share's drain), stages
 // their events in the due list after publishing, and the next round starts
 // its event loop right after the barrier.  Every append to a bin before
 // pf_lim, and every inbox append, is noted by its sender (note_dirty) and
@@ -1653,7 +1664,7 @@ __global__ __launch_bounds__(kBlock) void k_round_ps(uint64_t window, int nb, De
         uint64_t next = kInf;
         PfBins pb;
         uint64_t span = 0;
-        ps_loop_close<kPsPf>(P, c, active, has, R, lb, we, w, (uint32_t)(ws >> P.bin_shift) & (kNB - 1), clr, next, &pb,
+        ps_loop_close<kPsPf, false>(P, c, active, has, R, lb, we, w, (uint32_t)(ws >> P.bin_shift) & (kNB - 1), clr, next, &pb,
                              &span);
         acc[0] += c.c_events; acc[1] += c.c_pkt; acc[2] += c.c_sent;
         acc[3] += c.c_idrop; acc[4] += c.c_cdrop; acc[5] += c.c_recv;
@@ -1677,8 +1688,15 @@ __global__ __launch_bounds__(kBlock) void k_round_ps(uint64_t window, int nb, De
         uint64_t f_next, dm = 0;
         uint32_t f_fl, f_nev, f_npkt, f_nact;
         bool dall = false;
+#ifdef SHD_TIMING_LIGHT
+        uint32_t n_poll = 0;
+        const bool ok_v = ps_gather<kPsPf>(rs, 2 * nblk, base, nblk, tag, blockIdx.x == 0, ticks, f_next, f_fl, f_nev, f_npkt,
+                                           f_nact, hb, (uint32_t)P.hpw, &dm, &dall, &n_poll);
+        TIMVP(22, (uint64_t)n_poll);   // the gather's poll passes (k_round_sp: 22 is its own)
+#else
         const bool ok_v = ps_gather<kPsPf>(rs, 2 * nblk, base, nblk, tag, blockIdx.x == 0, ticks, f_next, f_fl, f_nev, f_npkt,
                                            f_nact, hb, (uint32_t)P.hpw, &dm, &dall);
+#endif
         TIMP(7);
         // the folds come out of ps_gather in scalar registers, so the round
         // loop and the parity branch stay scalar (with a vector exit condition
@@ -1855,7 +1873,7 @@ __device__ __forceinline__ void sp_scan(const DParams& P, const PsRsrc& R, uint3
 // lane's share (PEND: a logged first touch flags kPsPend)
 // (alist: the scan's list; lrec / lhn: the block's hosts' records and next
 // times in LDS, or null: the global ones)
-template <bool PEND>
+template <bool PEND, bool XCH = true>
 __device__ __forceinline__ void sp_passes(const DParams& P, HostCtx& c, const PsRsrc& R, uint32_t hb, uint32_t nact,
                                           uint64_t ws, uint64_t we, int parity, uint32_t xwi, uint64_t& next,
                                           uint32_t& nev, uint32_t& npkt, uint32_t& fl, uint32_t& nhost,
@@ -1892,7 +1910,7 @@ __device__ __forceinline__ void sp_passes(const DParams& P, HostCtx& c, const Ps
         }
         const uint32_t wbits = ps_window_bits(P, c, w, ws, we);
         uint64_t hn = kInf;
-        ps_round_body<true>(P, c, act, lb, R, ws, we, parity, nin, w, wbits, hn, &in);
+        ps_round_body<true, XCH>(P, c, act, lb, R, ws, we, parity, nin, w, wbits, hn, &in);
         if (act) {
             if (lrec) store_ctx(P, c, &lrec[lb], &lhn[lb]);
             else store_ctx(P, c);
@@ -1979,7 +1997,7 @@ __global__ __launch_bounds__(kBlock) void k_round_sp(uint64_t window, int nb, De
         TIMVP(21, (uint64_t)((nact + kBlock - 1) / kBlock));   // passes
         // the active hosts, 64 at a time
         uint32_t nev = 0, npkt = 0, fl = 0, nhost = 0;
-        sp_passes<true>(P, c, R, hb, nact, ws, we, parity, 0u, next, nev, npkt, fl, nhost, alist, lrec, lhn);
+        sp_passes<true, false>(P, c, R, hb, nact, ws, we, parity, 0u, next, nev, npkt, fl, nhost, alist, lrec, lhn);
         next = wave_min_u64(next);
         nev = wave_sum_u32(nev);
         npkt = wave_sum_u32(npkt);
