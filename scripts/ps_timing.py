@@ -10,7 +10,10 @@ Stamps (100 MHz wall clock; every stamp first drains the wave's memory ops):
 sorted, 3 last flush starts, 4 event loop + flushes done, 5 close done
 (bin resets, last deliveries), 6 share published (drained), 7 every share of
 the round seen; k_round_ps also 21 the last flush's claims back and its stores
-issued, 22 the gather's poll passes.  Printed relative to the round's earliest start: mean over
+issued, 22 the gather's poll passes, 23 the close's work under the last flush's
+path loads done (12 -> 23: the loads' issue and that work; 23 -> 13: what is
+left of their wait, and the resolve), 20 the round's end (what every block does
+between the gather's return and its next start).  Printed relative to the round's earliest start: mean over
 rounds of the mean and the max over blocks; and the phase durations.
 """
 import ctypes as C
@@ -134,6 +137,33 @@ def main():
               f"{np.mean([a.max() for a, _, _ in cr]):.2f} us; loop done -> there {np.mean([b.mean() for _, b, _ in cr]):.2f} us, "
               f"there -> close done {np.mean([c.mean() for _, _, c in cr]):.2f} us; publish drain (close done -> published) "
               f"mean {np.mean([d.mean() for d in dr]):.2f} / max {np.mean([d.max() for d in dr]):.2f} us")
+    # the close under the last flush's path loads (12 -> 23 -> 13), in blocks that flushed
+    gp = []
+    for r in range(64):
+        x = t_all[r]
+        t0 = x[:, 0].min()
+        ok = (t0 > 0) & (x[:, 12] >= t0) & (x[:, 23] >= x[:, 12]) & (x[:, 13] >= x[:, 23])
+        if ok.any():
+            gp.append(((x[ok, 23] - x[ok, 12]) / 100.0, (x[ok, 13] - x[ok, 23]) / 100.0))
+    if gp:
+        print(f"  last flush: loads issued + close under them mean {np.mean([a.mean() for a, _ in gp]):.2f} / max "
+              f"{np.mean([a.max() for a, _ in gp]):.2f} us, then their wait + resolve mean "
+              f"{np.mean([b.mean() for _, b in gp]):.2f} / max {np.mean([b.max() for _, b in gp]):.2f} us")
+    # behind the gather: all seen (7) -> the round's end (20) -> the block's next start (the next slot's 0)
+    ge, gs = [], []
+    for r in range(64):
+        x, y = t_all[r], t_all[(r + 1) % 64]
+        t0 = x[:, 0].min()
+        ok = (t0 > 0) & (x[:, 7] >= t0) & (x[:, 20] >= x[:, 7]) & (x[:, 20] - x[:, 7] < 10000)
+        if ok.any():
+            ge.append((x[ok, 20] - x[ok, 7]) / 100.0)
+        ok = ok & (y[:, 0] >= x[:, 20]) & (y[:, 0] - x[:, 20] < 10000)
+        if ok.any():
+            gs.append((y[ok, 0] - x[ok, 20]) / 100.0)
+    if ge and gs:
+        print(f"  behind the gather: all seen -> round's end mean {np.mean([a.mean() for a in ge]):.2f} / max "
+              f"{np.mean([a.max() for a in ge]):.2f} us, round's end -> next start mean "
+              f"{np.mean([a.mean() for a in gs]):.2f} / max {np.mean([a.max() for a in gs]):.2f} us")
     if npo:
         print(f"  gather poll passes per block and round: mean {np.mean([a.mean() for a in npo]):.2f}, max "
               f"{np.mean([a.max() for a in npo]):.2f}")

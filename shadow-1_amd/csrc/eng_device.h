@@ -1030,6 +1030,34 @@ __device__ __forceinline__ void path_load_flat(const DParams& P, int32_t a, int3
     x.rs = a == b ? rs : kNoRank;
 }
 
+// The same in two steps, so that a caller can put work between the loads'
+// issue and their first use (the persistent round's last flush, flush_last_issue)
+struct PathFlat {
+    shd_pv d, v1, v2, vs;
+    uint32_t adj;
+    int32_t rb, rs;
+};
+__device__ __forceinline__ void path_issue_flat(const DParams& P, int32_t a, int32_t b, PathFlat& f) {
+    const size_t ab = (size_t)a * P.T + b, ba = (size_t)b * P.T + a;
+    const bool use_dir = P.complete || P.prefer_direct, use_rows = !P.complete;
+    const size_t i_d = use_dir ? ab : 0, i_ab = use_rows ? ab : 0, i_ba = use_rows ? ba : 0;
+    const shd_pv* rowp = P.row ? (const shd_pv*)P.row : (const shd_pv*)P.dir;
+    f.d = P.dir[i_d];
+    f.adj = P.adj[i_d];
+    f.v1 = rowp[i_ab]; f.v2 = rowp[i_ba]; f.vs = P.self[a];
+    f.rb = P.rank[b]; f.rs = P.self_rank[a];
+}
+__device__ __forceinline__ void path_take_flat(const DParams& P, int32_t a, int32_t b, PathFlat f, PathRaw& x) {
+    f.d.lat = launder(f.d.lat); f.d.rel = launder(f.d.rel); f.adj = launder(f.adj);
+    f.v1.lat = launder(f.v1.lat); f.v1.rel = launder(f.v1.rel); f.v2.lat = launder(f.v2.lat); f.v2.rel = launder(f.v2.rel);
+    f.vs.lat = launder(f.vs.lat); f.vs.rel = launder(f.vs.rel); f.rb = launder(f.rb); f.rs = launder(f.rs);
+    x.d = f.d;
+    x.adj = P.prefer_direct ? f.adj : 0u;
+    x.v1 = f.v1;
+    x.v2 = a == b ? f.vs : f.v2;
+    x.rb = a == b ? kNoRank : f.rb;
+    x.rs = a == b ? f.rs : kNoRank;
+}
 __device__ __forceinline__ PathVal path_select(const DParams& P, int32_t a, int32_t b, int32_t ra, const PathRaw& x) {
     PathVal v;
     v.resolved = true;
@@ -1117,6 +1145,12 @@ __device__ __forceinline__ bool send_room() {
 __device__ __forceinline__ void send_pool_reset(HostCtx& c) {
     c.ns = 0;
     s_pool_n = 0;
+}
+
+// the deferred sends of the wave (wave-uniform)
+__device__ __forceinline__ uint32_t flush_total() {
+    const uint32_t claimed = __hip_atomic_load(&s_pool_n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    return __builtin_amdgcn_readfirstlane(claimed < (uint32_t)kPool ? claimed : (uint32_t)kPool);
 }
 
 // loopback test of a destination draw (network_interface.c:548-555): the
@@ -1386,6 +1420,174 @@ __device__ __forceinline__ void flush_finish(const DParams& P, HostCtx& c, const
         return;
     }
     emit_nocal<XCH>(P, c, e);
+}
+
+// The steps of flush_wave on their own, for the two-step last flush below (which
+// takes one record per lane).  The walk: each host walks its own sends in send order
+// (worker.c:286-320): event IDs, counters, traces, first-touch logs; s_res
+// then holds the events to deliver.  Timers scheduled since the last flush
+// hold provisional IDs: an ID x loses the dropped sends issued before it
+template <bool PS>
+__device__ __forceinline__ void flush_walk(const DParams& P, HostCtx& c, uint32_t n) {
+    const uint32_t lane = threadIdx.x;
+    uint32_t nfail = 0;
+    uint64_t f0 = 0, f1 = 0, f2 = 0;
+    const bool p0 = c.tt0 != kInf && c.ts0 >= c.seq_base, p1 = c.tt1 != kInf && c.ts1 >= c.seq_base,
+               p2 = c.tt2 != kInf && c.ts2 >= c.seq_base;
+    uint32_t k = n ? s_shd[lane] : 0u;
+    for (uint32_t i = 0; i < n; i++) {
+        shd_event e = s_res[k];
+        const SendRec q = s_send[k];
+        const bool pass = e.kind & 1u, log = (e.kind & 2u) != 0, resolved = (e.kind & 4u) != 0;
+        const int32_t b = (int32_t)e.src;
+        uint32_t emit = 0;
+        if (pass) {
+            const uint64_t seq = c.seq_base + q.pseq - nfail;
+            trace(P, c, q.now, seq, c.h, e.dst, q.pkt, SHD_TR_SENT);
+            c.c_sent++;
+            // 1 = delivery waits for the resolution, 2 = already delivered
+            if (log) log_pending(P, c, q, c.att, b, resolved ? 2u : 1u, e.dst, seq, PS ? s_rsum : P.sum);
+            if (resolved && e.time < c.k.end_time) {   // scheduler_push drops time >= end
+                emit = SHD_EV_PACKET;
+                if (e.time < c.min_emit) c.min_emit = e.time;
+            }
+            e.seq = seq;
+        } else {
+            trace(P, c, q.now, 0, c.h, e.dst, q.pkt, SHD_TR_INET_DROP);
+            c.c_idrop++;
+            if (log) log_pending(P, c, q, c.att, b, 0u, e.dst, 0, PS ? s_rsum : P.sum);
+            const uint64_t xi = c.seq_base + q.pseq;
+            f0 += xi < c.ts0; f1 += xi < c.ts1; f2 += xi < c.ts2;
+            nfail++;
+        }
+        e.src = c.h;
+        e.pkt = q.pkt;
+        e.kind = emit;
+        s_res[k] = e;
+        k = q.next;
+    }
+    if (nfail) {
+        if (p0) c.ts0 -= f0;
+        if (p1) c.ts1 -= f1;
+        if (p2) c.ts2 -= f2;
+        c.ev_seq -= nfail;
+    }
+    c.seq_base = c.ev_seq;
+    c.ns = 0;
+}
+
+// the destination host of a deferred send and its attached index (hl: the
+// sender's lane)
+__device__ __forceinline__ void flush_dest(const DParams& P, const SendRec& q, uint32_t hl, int32_t& dst, int32_t& b) {
+    if (q.r & kDstHost) {   // a destination the application named (UDP echo)
+        dst = (int32_t)(q.r & ~kDstHost);
+        b = P.host_att[dst];
+    } else if (P.dest_closed) {   // no table: one memory round trip fewer
+        dst = closed_dest(P, q.r);
+        b = dst;
+    } else {
+        const double rr = (double)q.r / kRandMax;
+        const size_t row = (size_t)s_cls[hl] * (size_t)P.H;
+        const uint4* gq = (const uint4*)(P.dest_guide + row + guide_index(P, rr));
+        const uint4 g0 = gq[0], g1 = gq[1], g2 = gq[2];
+        guide_pick(P, P.dest_cum + row, g0, g1, g2, rr, dst, b);
+    }
+}
+// the path's candidates at hand: the rank rule, the drop test and the arrival
+// time; the record for the per-host walk.  True: the send passed, is
+// resolved and arrives before the end (a delivery)
+__device__ __forceinline__ bool flush_resolved(const DParams& P, HostCtx& c, const SendRec& q, int32_t a, int32_t b,
+                                               int32_t dst, int32_t ra_l, const PathRaw& x, uint32_t& err, shd_event& e) {
+    const int32_t ra = P.complete ? kNoRank : ra_l;
+    const PathVal pv = path_select(P, a, b, ra, x);
+    const double chance = (double)q.chance / kRandMax;
+    const bool boot = (q.q_sub >> 31) != 0;
+    const bool pass = boot || chance <= pv.rel || P.payload == 0;
+    if (!pv.resolved) {
+        const bool pass2 = boot || chance <= pv.rel2 || P.payload == 0;
+        if (pass != pass2 || (c.k.feat & F_AMBIG)) err |= SHD_ERR_AMBIGUOUS;
+    }
+    if ((c.k.feat & F_PCOUNT) && pass && pv.resolved) atomicAdd(&P.pcount[path_key(P, a, b, ra, x.rb, x.adj)], 1u);
+    e.time = q.now + (uint64_t)ceil(pv.lat * (double)SHD_MS);
+    e.seq = 0;
+    e.src = (uint32_t)b;   // the destination's attached index, for the first-touch log
+    e.dst = (uint32_t)dst;
+    e.pkt = 0;
+    e.kind = (pass ? 1u : 0u) | (pv.log ? 2u : 0u) | (pv.resolved ? 4u : 0u);
+    return pass && pv.resolved && e.time < c.k.end_time;
+}
+// a delivery of the round's last flush (one batch: record r is lane r's): the
+// calendar claim goes out in the resolve, under the per-host walk; the store
+// follows in flush_finish
+__device__ __forceinline__ void flush_claim(const DParams& P, HostCtx& c, const shd_event& e, PendDel& pd) {
+    const int32_t dl = (int32_t)e.dst - P.h0;
+    const uint64_t bb = e.time >> P.bin_shift;
+    pd.kind = 2;
+    if (P.bins && dl >= 0 && dl < P.nloc && bb - (c.ws >> P.bin_shift) <= kHorizon) {
+        pd.bi = (size_t)dl * kNB + ((uint32_t)bb & (kNB - 1));
+        pd.slot = atomicAdd(&P.bin_n[pd.bi], 1u);
+        pd.kind = 1;
+        pd.near = bb < c.pf_lim ? 1u : 0u;
+    }
+}
+
+// The persistent rounds' last flush of one batch (0 < total <= kBlock), in
+// two steps with the round's close between them: the path loads take one
+// memory round trip, and the close needs nothing of the flush but min_emit.
+// The issue step: the send record, its destination and every load of the
+// path lookup -- under the lane's own `valid`, into values that live outside
+// the branch, and not yet used: the first use waits for them
+struct LastFlush {
+    SendRec q;
+    int32_t a, b, dst, ra;
+    PathFlat f;
+    bool valid;
+};
+__device__ __forceinline__ void flush_last_issue(const DParams& P, HostCtx& c, uint32_t total, LastFlush& s) {
+    const uint32_t lane = threadIdx.x;
+    s_att[lane] = c.att;
+    s_cls[lane] = c.cls;
+    __syncthreads();
+#ifdef SHD_TIMING_LIGHT
+    TIMP(12);
+#endif
+    s.valid = lane < total;
+    s.q = SendRec{};
+    s.a = 0; s.b = 0; s.dst = 0; s.ra = 0;
+    s.f = PathFlat{};
+    if (s.valid) {
+        s.q = s_send[lane];
+        s.a = s_att[s.q.lane];
+        flush_dest(P, s.q, s.q.lane, s.dst, s.b);
+        s.ra = P.rank[s.a];
+        path_issue_flat(P, s.a, s.b, s.f);
+    }
+}
+// the consume step: the loads' wait, the rank rule, the drop test, the
+// calendar claim; then the per-host walk.  s_res[lane] stays for flush_finish
+template <bool PS>
+__device__ __forceinline__ void flush_last_consume(const DParams& P, HostCtx& c, LastFlush& s, PendDel& pd) {
+    uint32_t err = 0;
+    if (s.valid) {
+        PathRaw x;
+        path_take_flat(P, s.a, s.b, s.f, x);
+        const int32_t ra_l = launder(s.ra);
+        shd_event e;
+        const bool del = flush_resolved(P, c, s.q, s.a, s.b, s.dst, ra_l, x, err, e);
+        s_res[threadIdx.x] = e;
+        if (del) flush_claim(P, c, e, pd);
+    }
+    __syncthreads();
+#ifdef SHD_TIMING_LIGHT
+    TIMP(13);
+#endif
+    flush_walk<PS>(P, c, c.ns);
+    __syncthreads();
+    if (threadIdx.x == 0) s_pool_n = 0;
+#ifdef SHD_TIMING_LIGHT
+    TIMP(14);
+#endif
+    c.err |= err;
 }
 
 // _networkinterface_sendPackets (network_interface.c:519-579), FIFO qdisc.

@@ -1173,19 +1173,25 @@ struct PfBins {
     EvV x[kPfBins][kBinCap];
     uint32_t m;   // bit j: bin b + j was loaded
 };
-// (sp: the bitmap's span from bin b on, bm_span)
+// (sp: the bitmap's span from bin b on, bm_span).  Every lane issues every
+// load, whatever its bitmap says: a lane without the bin reads past the
+// resource's end, which the buffer's range check answers with zeros and no
+// memory access.  So the compiler knows how many loads these are, and a wait
+// for loads issued ahead of them (the last flush's path loads, ps_loop_close)
+// does not take these in -- behind loads under a branch it would wait for all
+constexpr uint32_t kPfPast = 0x40000000u;   // past any block's bins (64 hosts: 2 MB)
 __device__ __forceinline__ void pf_issue(const PsRsrc& R, uint32_t lb, uint64_t b, uint64_t sp, bool has, PfBins& pb) {
+    static_assert((uint64_t)kBlock * kNB * kBinCap * sizeof(shd_event) <= kPfPast, "past the end");
     pb.m = 0;
-    if (!has) return;
 #pragma unroll
     for (uint32_t j = 0; j < kPfBins; j++) {
         const uint32_t p = (uint32_t)(b + j) & (kNB - 1);
-        if (!((sp >> j) & 1ull)) continue;
-        pb.m |= 1u << j;
+        const bool on = has && ((sp >> j) & 1ull);
+        pb.m |= on ? 1u << j : 0u;
         const uint32_t bi = lb * kNB + p;
 #pragma unroll
         for (uint32_t k = 0; k < kBinCap; k++) {
-            const uint32_t off = (bi * kBinCap + k) * 32u;
+            const uint32_t off = on ? (bi * kBinCap + k) * 32u : kPfPast;
             pb.x[j][k] = EvV{ld16_sc1(R.bins, off), ld16_sc1(R.bins, off + 16)};
         }
     }
@@ -1244,17 +1250,25 @@ __device__ __forceinline__ uint64_t cal_lower_bound_sp(const DParams& P, const u
 
 // The round's event loop (as round_body's: per-lane state 0 needs its next
 // event, 1 runs one, 2 waits for a flush, 3 done; wave-uniform exits only)
-// and its close: the last flush's stores, then the lane's next time (an idle
-// lane's from its timers and bitmap).  PF: clr (bit j: ring position clr_p + j)
+// and its close: the lane's next time (an idle lane's from its timers and
+// bitmap), worked out under the last flush's path loads, then the last
+// flush's stores.  PF: clr (bit j: ring position clr_p + j)
 // is cleared from w first (bins the prologue reset, when w was loaded in
-// parallel), and the next window's bins are loaded between the loop and the
-// close, into *pb; *span: the bitmap's span from we's bin on, for the next round.
-template <bool PF, bool XCH = true>
+// parallel), and the next window's bins are loaded in the close, into *pb;
+// *span: the bitmap's span from we's bin on, for the next round.  fin: the
+// caller's own work on what is final once the loop has ended (the whole wave
+// calls it, in the close)
+struct PsNoFin {
+    __device__ __forceinline__ void operator()() const {}
+};
+template <bool PF, bool XCH = true, class Fin = PsNoFin>
 __device__ __forceinline__ void ps_loop_close(const DParams& P, HostCtx& c, bool active, bool has, const PsRsrc& R,
                                               uint32_t lb, uint64_t we, uint32_t (&w)[kNBW], uint32_t clr_p,
-                                              uint32_t clr, uint64_t& next, PfBins* pb, uint64_t* span) {
+                                              uint32_t clr, uint64_t& next, PfBins* pb, uint64_t* span,
+                                              const Fin& fin = Fin{}) {
     PendDel pd;
     pd.kind = 0;
+    uint32_t total = 0;   // the sends of a last flush of one batch
 #ifdef SHD_TIMING_LIGHT
     uint32_t n_it = 0, n_fl = 0;
     unsigned long long t_take = 0, t_work = 0, t_fl = 0, ta = 0, t_q[3] = {0, 0, 0};
@@ -1336,7 +1350,15 @@ __device__ __forceinline__ void ps_loop_close(const DParams& P, HostCtx& c, bool
             n_fl++;
             ta = wall_clock64();
 #endif
-            flush_wave<true, XCH>(P, c, last, pd);
+            // PF: the round's last flush, when it is one batch, is taken below,
+            // in two steps around the close; of more than one batch: here,
+            // whole (not deferred: its deliveries go out with it)
+            if (PF && last) {
+                total = flush_total();
+                if (total <= (uint32_t)kBlock) break;
+                total = 0;
+            }
+            flush_wave<true, XCH>(P, c, !PF && last, pd);
 #ifdef SHD_TIMING_LIGHT
             if (!last) t_fl += wall_clock64() - ta;
 #endif
@@ -1344,27 +1366,40 @@ __device__ __forceinline__ void ps_loop_close(const DParams& P, HostCtx& c, bool
             if (st == 2u) st = 1u;
         }
     }
-    TIMP(4);
+    const auto loop_done = [&]() {
+        TIMP(4);
 #ifdef SHD_TIMING_LIGHT
-    TIMVP(16, (uint64_t)n_it);   // loop iterations of the wave
-    TIMVP(17, (uint64_t)n_fl);   // flushes
-    TIMVP(18, (uint64_t)__popcll(__ballot(active)));
-    TIMVP(8, t_take);    // in take_next + begin_event (+ the fused notification / refill)
-    TIMVP(9, t_work);    // in run_work
-    TIMVP(10, t_fl);     // in the flushes before the last
-    TIMVP(11, t_q[0]);   // of 8: take_next
-    TIMVP(15, t_q[1]);   //       begin_event
-    TIMVP(19, t_q[2]);   //       the fused notification (the rest: the fused refill, the loop's own)
+        TIMVP(16, (uint64_t)n_it);   // loop iterations of the wave
+        TIMVP(17, (uint64_t)n_fl);   // flushes
+        TIMVP(18, (uint64_t)__popcll(__ballot(active)));
+        TIMVP(8, t_take);    // in take_next + begin_event (+ the fused notification / refill)
+        TIMVP(9, t_work);    // in run_work
+        TIMVP(10, t_fl);     // in the flushes before the last
+        TIMVP(11, t_q[0]);   // of 8: take_next
+        TIMVP(15, t_q[1]);   //       begin_event
+        TIMVP(19, t_q[2]);   //       the fused notification (the rest: the fused refill, the loop's own)
 #endif
-    // the last flush's stores first: they wait for the calendar claims alone
-    // (issued in the resolve loop, nothing behind them in the queue yet), and
-    // their write-through runs under the close instead of in front of the
-    // share's drain.  A delivery into a bin loaded ahead below is noted here,
-    // before ps_noted reads the list.
-    flush_finish<XCH>(P, c, pd);
-#ifdef SHD_TIMING_LIGHT
-    if (PF) TIMP(21);   // the claims are back, the last flush's stores issued (k_round_sp: 20, 21 are its own)
-#endif
+    };
+    // PF (k_round_ps): the last flush's path loads go out first and the close
+    // runs while they are in flight: it needs nothing of the flush but
+    // min_emit, and the flush nothing of it (pf_lim is the round's).  The next
+    // window's bins may so be loaded ahead of this wave's own deliveries into
+    // them: those are noted as every other block's (note_dirty in
+    // flush_finish, before ps_noted reads the list), and a noted host reads
+    // its window again.  The prefetch loads follow the path loads (ahead of
+    // them they delay the resolve by their own round trip: loads return in
+    // order), and are countable (pf_issue), so the resolve waits for the path
+    // loads alone.
+    // Not PF (k_round_sp's passes: a few sends each and next to no close to put
+    // under them; the split measured 2 % slower there): the last flush's stores,
+    // then the close.
+    LastFlush lf;
+    if (PF) {
+        if (total) flush_last_issue(P, c, total, lf);
+    } else {
+        loop_done();
+        flush_finish<XCH>(P, c, pd);
+    }
     uint64_t sp = 0;
     if (PF) {
         bm_clear(w, clr_p, clr);
@@ -1373,20 +1408,28 @@ __device__ __forceinline__ void ps_loop_close(const DParams& P, HostCtx& c, bool
         *span = sp;
         pf_issue(R, lb, b1, sp, has, *pb);
     }
-    if (active) {
-        next = host_next(c);
-        if (c.min_emit < next) next = c.min_emit;
-        if (P.bins) {   // (the consumed bins were cleared in w)
-            const uint64_t cb = cal_lower_bound_sp<PF>(P, w, sp, we);
-            next = cb < next ? cb : next;
-        }
-    } else if (has) {
+    if (has) {   // (an idle lane's from its timers and bitmap; the consumed bins were cleared in w)
         next = host_next(c);
         if (P.bins) {
             const uint64_t cb = cal_lower_bound_sp<PF>(P, w, sp, we);
             next = cb < next ? cb : next;
         }
     }
+    fin();
+    if (PF) {
+#ifdef SHD_TIMING_LIGHT
+        TIMP(23);   // the close's work under the path loads done: their wait is next (k_round_sp: 23 is its own)
+#endif
+        if (total) flush_last_consume<true>(P, c, lf, pd);
+        loop_done();
+        // the stores wait for the calendar claims alone; a delivery into a
+        // bin loaded ahead is noted here
+        flush_finish<XCH>(P, c, pd);
+#ifdef SHD_TIMING_LIGHT
+        TIMP(21);   // the claims are back, the last flush's stores issued (k_round_sp: 20, 21 are its own)
+#endif
+    }
+    if (active && c.min_emit < next) next = c.min_emit;
     TIMP(5);
 }
 
@@ -1664,17 +1707,21 @@ __global__ __launch_bounds__(kBlock) void k_round_ps(uint64_t window, int nb, De
         uint64_t next = kInf;
         PfBins pb;
         uint64_t span = 0;
+        // the share's counts are final once the loop has ended: folded in the
+        // close, under the last flush's loads (the walk counts sends and drops only)
+        uint32_t nev = 0, npkt = 0, nact = 0;
+        const auto fin = [&]() {
+            acc[0] += c.c_events; acc[1] += c.c_pkt; acc[4] += c.c_cdrop; acc[5] += c.c_recv;
+            nact = (uint32_t)__popcll(__ballot(c.c_events != 0));
+            nev = wave_sum_u32(c.c_events);
+            npkt = wave_sum_u32(c.c_pkt);
+        };
         ps_loop_close<kPsPf, false>(P, c, active, has, R, lb, we, w, (uint32_t)(ws >> P.bin_shift) & (kNB - 1), clr, next, &pb,
-                             &span);
-        acc[0] += c.c_events; acc[1] += c.c_pkt; acc[2] += c.c_sent;
-        acc[3] += c.c_idrop; acc[4] += c.c_cdrop; acc[5] += c.c_recv;
-        uint32_t nev = c.c_events, npkt = c.c_pkt, err = c.err;
+                                    &span, fin);
+        acc[2] += c.c_sent; acc[3] += c.c_idrop;
         const uint32_t pend = c.n_pend ? kPsPend : 0u;
-        const uint32_t nact = (uint32_t)__popcll(__ballot(nev != 0));
-        const uint32_t fl = wave_or_u32(err | pend);
+        const uint32_t fl = wave_or_u32(c.err | pend);
         next = wave_min_u64(next);
-        nev = wave_sum_u32(nev);
-        npkt = wave_sum_u32(npkt);
         const uint32_t tag = tag0 + (uint32_t)i;
         const uint32_t base = (uint32_t)(i & 1) * nblk;
         ps_publish(rs, 2 * nblk, base + blockIdx.x, next, fl, nev, npkt, nact, tag, ps_noted(pfm));
@@ -1727,6 +1774,9 @@ __global__ __launch_bounds__(kBlock) void k_round_ps(uint64_t window, int nb, De
         if (ws >= stop) break;      // the rest only forwards the time (ring[i + 1].next_time says so)
         pf = pfm;
         dirty = (dall || ((dm >> lb) & 1ull)) ? 1u : 0u;
+#ifdef SHD_TIMING_LIGHT
+        TIMP(20);   // the round's end: the summary and the exit tests behind the gather (k_round_sp: 20 is its own)
+#endif
     }
     // the hosts' state, once for the whole batch
     if (has) {
