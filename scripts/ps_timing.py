@@ -5,6 +5,10 @@ the timing build:
     make -C shadow-1_amd timing TIMING_FLAGS=-DSHD_TIMING_LIGHT
     SHDGPU_LIB=shadow-1_amd/libshdgpu_tim.so python3 scripts/ps_timing.py
 
+With -DSHD_TIMING_NOLOOP added the event loop has no clock read inside (its
+per-part shares then read 0.00); the stamps and the iteration count stay, and
+the slope printed under "per iteration" is the product's cost of one iteration.
+
 Stamps (100 MHz wall clock; every stamp first drains the wave's memory ops):
 0 round start, 1 hand-off words read (idle test; k_round_sp: the scan and compaction), 2 bins + inbox merged and
 sorted, 3 last flush starts, 4 event loop + flushes done, 5 close done
@@ -169,12 +173,13 @@ def main():
               f"{np.mean([a.max() for a in npo]):.2f}")
     # the event loop: iterations (16), flushes (17), active lanes (18) per block and round, and
     # how the loop's length (stamp 2 -> 4) follows them
-    it, nfl, nact, dur, seg = [], [], [], [], []
+    it, nfl, nact, dur, seg, lend = [], [], [], [], [], []
     for r in range(64):
         x = t_all[r]
         t0 = x[:, 0].min()
         ok = (t0 > 0) & (x[:, 4] >= x[:, 2]) & (x[:, 2] >= t0) & (x[:, 16] < 10000)
         it += list(x[ok, 16]); nfl += list(x[ok, 17]); nact += list(x[ok, 18])
+        lend += list(np.where(x[ok, 3] >= x[ok, 2], (x[ok, 3] - x[ok, 2]) / 100.0, np.nan))
         seg += [list(v) for v in x[ok][:, [8, 9, 10, 11, 15, 19]] / 100.0]
         dur += list((x[ok, 4] - x[ok, 2]) / 100.0)
     if it:
@@ -187,6 +192,20 @@ def main():
                   f"(take+begin {seg[sel, 0].mean():.2f} = take_next {seg[sel, 3].mean():.2f} + begin_event "
                   f"{seg[sel, 4].mean():.2f} + notify {seg[sel, 5].mean():.2f} + rest; run_work "
                   f"{seg[sel, 1].mean():.2f}, early flushes {seg[sel, 2].mean():.2f}), flushes {nfl[sel].mean():.2f}")
+        # the cost of one iteration: the least-squares slope over the block-rounds with one flush of
+        # (loop done - bins merged), stamps 2 -> 4, and of the loop alone (bins merged -> the last flush
+        # starts, 2 -> 3), against the iteration count.  A build with -DSHD_TIMING_NOLOOP has no clock
+        # read inside the loop: its slope is the product's.
+        lend = np.array(lend)
+        one = (nfl == 1) & (it >= 1)
+        if len(set(it[one].tolist())) > 1:
+            s4, i4 = np.polyfit(it[one], dur[one], 1)
+            line = f"    per iteration (slope over {int(one.sum())} block-rounds): loop done - bins merged {s4:.3f} us (+ {i4:.2f})"
+            ok3 = one & ~np.isnan(lend)
+            if len(set(it[ok3].tolist())) > 1:
+                s3, i3 = np.polyfit(it[ok3], lend[ok3], 1)
+                line += f"; last flush starts - bins merged {s3:.3f} us (+ {i3:.2f})"
+            print(line)
     # k_round_sp: active hosts (20) and passes (21) per block and round
     na, npas = [], []
     for r in range(64):

@@ -1195,7 +1195,9 @@ __device__ __forceinline__ void guide_pick(const DParams& P, CumPtr cum, uint4 g
 
 // worker_sendPacket (worker.c:260-321), deferred: the reliability draw is
 // made now (it is drawn for every non-loopback send, worker.c:286); the
-// path lookup, the drop decision and the delivery happen at the next flush
+// path lookup, the drop decision and the delivery happen at the next flush.
+// (worker_send_placed below builds the same record for steady_iter: change
+// both together.)
 __device__ void worker_send_deferred(const DParams& P, HostCtx& c, uint32_t rv, uint32_t pkt) {
     const uint32_t chance = (uint32_t)rand_r_dev(c.rng);
     SendRec q;
@@ -1214,6 +1216,31 @@ __device__ void worker_send_deferred(const DParams& P, HostCtx& c, uint32_t rv, 
     c.ns++;
     c.ev_seq++;   // provisional: a dropped send gives its ID back at the flush
     c.if_out++;   // tracker_addOutputBytes (network_interface.c:571)
+}
+
+// worker_send_deferred with the record's place k in the pool and the lane's
+// last record stl given (steady_iter: one wave a block, so the place is the
+// pool count plus the lane's rank among the lanes sending, and s_stl was read
+// ahead): the same record, the same links, the same counters -- a change to
+// either copy goes into the other
+__device__ __forceinline__ void worker_send_placed(const DParams& P, HostCtx& c, uint32_t rv, uint32_t pkt, uint32_t k,
+                                                   uint32_t stl) {
+    const uint32_t chance = (uint32_t)rand_r_dev(c.rng);
+    SendRec q;
+    q.now = c.now; q.q_seq = c.q_seq; q.q_src = c.q_src;
+    q.pseq = (uint32_t)(c.ev_seq - c.seq_base);
+    q.r = rv; q.chance = chance; q.pkt = pkt;
+    q.q_sub = (c.q_sub++ & 0x7FFFFFFFu) | (bootstrapping(P, c) ? 0x80000000u : 0u);
+    q.lane = (uint16_t)threadIdx.x;
+    q.next = 0xFFFFu;
+    q._pad = 0;
+    s_send[k] = q;
+    if (c.ns) s_send[stl].next = (uint16_t)k;
+    else s_shd[threadIdx.x] = (uint16_t)k;
+    s_stl[threadIdx.x] = (uint16_t)k;
+    c.ns++;
+    c.ev_seq++;
+    c.if_out++;
 }
 
 // Resolve every lane's deferred sends together.  Called by all lanes of the
@@ -1763,7 +1790,13 @@ __device__ __forceinline__ bool notify_fast_ok(const DParams& P, const HostCtx& 
     return c.unread == 1u && c.tq_count == 0 && c.tx_rem >= SHD_MTU && send_room() &&
            !(c.k.feat & F_TRACE) && !bootstrapping(P, c);
 }
-__device__ __forceinline__ void notify_fast(const DParams& P, HostCtx& c) {
+// (room: send_room(), read by the caller)
+__device__ __forceinline__ bool notify_fast_ok_room(const DParams& P, const HostCtx& c, bool room) {
+    return c.unread == 1u && c.tq_count == 0 && c.tx_rem >= SHD_MTU && room && !(c.k.feat & F_TRACE) &&
+           !bootstrapping(P, c);
+}
+template <class Send>
+__device__ __forceinline__ void notify_fast_with(const DParams& P, HostCtx& c, const Send& send) {
     c.flags &= ~F_NOTIFY_PENDING;
     c.unread = 0;
     uint32_t rv, pkt;
@@ -1774,11 +1807,14 @@ __device__ __forceinline__ void notify_fast(const DParams& P, HostCtx& c) {
             c.tq_count = 1;
             c.w_fl = W_SENDING;
         } else {
-            worker_send_deferred(P, c, rv, pkt);
+            send(rv, pkt);
             consume(c.tx_rem, c.k.pkt_len);
             refill_if_needed(P, c);
         }
     }
+}
+__device__ __forceinline__ void notify_fast(const DParams& P, HostCtx& c) {
+    notify_fast_with(P, c, [&](uint32_t rv, uint32_t pkt) { worker_send_deferred(P, c, rv, pkt); });
 }
 
 // the periodic refill with both queues empty: top up; the receive loop's
@@ -1812,7 +1848,8 @@ __device__ void begin_event(const DParams& P, HostCtx& c, const shd_event& e) {
     // (sojourn 0: CoDel's interval and drop mode reset) and received; the
     // epoll notification is scheduled at +1 ns unless one is pending (its ID
     // is consumed even when it falls past the end).  The same steps as the
-    // general path below, in the same order.
+    // general path below, in the same order.  (arrival_fast_ok / arrival_fast
+    // below restate this test and body for steady_iter: change both together.)
     if (e.kind == SHD_EV_PACKET && c.cq_count == 0 && c.rx_rem >= SHD_MTU && (c.flags & F_LISTENING) &&
         !(c.k.feat & F_TRACE) && !bootstrapping(P, c)) {
         c.c_pkt++;
@@ -2114,6 +2151,124 @@ __device__ __forceinline__ bool take_next(const DParams& P, HostCtx& c, uint64_t
     if (c.tt0 == t) { e.seq = c.ts0; e.kind = SHD_EV_HEARTBEAT; c.tt0 = kInf; }
     else if (c.tt1 == t) { e.seq = c.ts1; e.kind = SHD_EV_REFILL; c.tt1 = kInf; }
     else { e.seq = c.ts2; e.kind = SHD_EV_NOTIFY; c.tt2 = kInf; }
+    return true;
+}
+
+// begin_event's steady-state arrival as a test and a body of its own, for
+// steady_iter (begin_event keeps its text: the kernels that do not take the
+// steady iteration compile as before): the same test, the same steps in the
+// same order -- a change to either copy goes into the other
+__device__ __forceinline__ bool arrival_fast_ok(const DParams& P, const HostCtx& c) {
+    return c.cq_count == 0 && c.rx_rem >= SHD_MTU && (c.flags & F_LISTENING) && !(c.k.feat & F_TRACE) &&
+           !bootstrapping(P, c);
+}
+__device__ __forceinline__ void arrival_fast(const DParams& P, HostCtx& c, uint32_t src) {
+    c.c_pkt++;
+    c.c_recv++;
+    c.if_in++;
+    c.unread++;
+    if ((c.k.feat & F_APP) && app_dest(c.flags) == SHD_DEST_REPLY) rq_push(P, c, src);
+    c.cq_head = (c.cq_head + 1 == c.k.cq_cap) ? 0 : c.cq_head + 1;
+    c.cq_iexp = 0;
+    const bool nt = !(c.flags & F_NOTIFY_PENDING);
+    if (nt && c.tt2 != kInf) c.err |= SHD_ERR_INTERNAL;
+    const uint64_t id = c.ev_seq, tn = c.now + 1;
+    c.ev_seq += nt ? 1u : 0u;
+    const bool set = nt && tn < c.k.end_time;
+    c.tt2 = set ? tn : c.tt2;
+    c.ts2 = set ? id : c.ts2;
+    c.flags = (c.flags & ~F_CODEL_DROP_MODE) | F_NOTIFY_PENDING;
+    consume(c.rx_rem, c.k.pkt_len);
+    refill_if_needed(P, c);
+}
+
+// The steady iteration of the persistent round's event loop (the lean
+// k_round_ps), ahead of take_next + begin_event: a lane whose next event is the
+// unique earliest of the five candidates, before `we`, and is an arrival, the
+// notification or the refill in the state their straight-line paths require
+// (arrival_fast_ok, notify_fast_ok, refill_fast's empty queues) runs, in one
+// fixed order and each at most once, the arrival, then the notification (its
+// own event, or the one at +1 ns behind the arrival when that is strictly the
+// host's next and in the window), then the refill under the same rule: what
+// take_next, begin_event and the loop's fused notification and refill do for
+// it, with the same functions in the same order (but the send's place in the
+// pool: worker_send_placed).  True for the lanes that took it (a lane with
+// nothing left before `we` among them: it is done); the others (a tie, a heap
+// event, a backlog, a full pool, a lane at work) are left untouched for the
+// general iteration.  The choice is per lane: per wave, by one ballot, so that
+// one lane that cannot sends the wave's iteration the general way, measured
+// no better.
+__device__ __forceinline__ bool steady_iter(const DParams& P, HostCtx& c, uint64_t we, uint32_t& st) {
+    const uint64_t ht = c.evq_n ? c.top_time : kInf;
+    const uint64_t m01 = c.tt0 < c.tt1 ? c.tt0 : c.tt1;
+    const uint64_t bt = m01 < c.tt2 ? m01 : c.tt2;
+    const uint64_t qt = c.dt < ht ? c.dt : ht;
+    const uint64_t t = bt < qt ? bt : qt;
+    const uint32_t neq = (uint32_t)(c.tt0 == t) + (uint32_t)(c.tt1 == t) + (uint32_t)(c.tt2 == t) +
+                         (uint32_t)(c.dt == t) + (uint32_t)(ht == t);
+    const bool u = st == 0u && t < we && neq == 1u;
+    // every LDS word the iteration reads goes out here, in one round trip: the
+    // due head (dt == t) and the time behind it (due_advance's), the pool
+    // count (send_room's: no lane of the steady body sends before the
+    // notification, and each once there) and the lane's last record
+    const shd_event d = s_due[(c.dh < c.nd ? c.dh : 0u) * kBlock + threadIdx.x];
+    const uint64_t dt1 = s_due[(c.dh + 1 < c.nd ? c.dh + 1 : 0u) * kBlock + threadIdx.x].time;
+    const uint32_t pn = __hip_atomic_load(&s_pool_n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    const uint32_t stl = s_stl[threadIdx.x];
+    const bool room = pn + (uint32_t)kBlock <= (uint32_t)kPool;
+    const uint64_t now0 = c.now;
+    c.now = t;   // the tests are the event's own
+    const bool sa = u && c.dt == t && d.kind == SHD_EV_PACKET && arrival_fast_ok(P, c);
+    const bool sn = u && c.tt2 == t && notify_fast_ok_room(P, c, room);
+    const bool sr = u && c.tt1 == t && c.cq_count == 0 && c.tq_count == 0;
+    const bool end = st == 0u && t >= we;   // nothing left before the window's end: the lane is done
+    c.now = now0;
+    const bool sdy = sa || sn || sr || end;
+    if (!sdy) return false;
+    if (end) st = 3u;
+    if (sa) {
+        c.dh++;
+        c.dt = c.dh < c.nd ? dt1 : kInf;
+        c.now = t; c.c_events++;
+        c.q_seq = d.seq; c.q_src = d.src; c.q_sub = 0;
+        c.w_msgs = 0; c.w_fl = 0;
+        arrival_fast(P, c, d.src);
+    }
+    bool dn = sn;
+    if (sa && c.tt2 < we) {
+        const uint64_t t2 = c.tt2;
+        dn = t2 < c.tt0 && t2 < c.tt1 && t2 < c.dt && t2 < ht && notify_fast_ok_room(P, c, room);
+    }
+    if (dn) {
+        c.now = c.tt2; c.tt2 = kInf; c.c_events++;
+        c.q_seq = c.ts2; c.q_src = c.h; c.q_sub = 0;
+        c.w_msgs = 0; c.w_fl = 0;
+        // The one send site of the steady body, and it must stay the only one:
+        // the slots are pn (the pool count read at the top, before any lane of
+        // this body sent) plus the rank among the lanes that reach this point
+        // together, and the first of them stores the new count.  A second
+        // send, or a send between the read of pn and here, would hand out the
+        // same slots twice.
+        notify_fast_with(P, c, [&](uint32_t rv, uint32_t pkt) {
+            const uint64_t m = __ballot(true);   // the lanes sending here
+            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+            worker_send_placed(P, c, rv, pkt, pn + rank, stl);
+            if (rank == 0)
+                __hip_atomic_store(&s_pool_n, pn + (uint32_t)__popcll(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        });
+        st = c.w_fl ? 1u : 0u;
+    }
+    bool dr = sr;
+    if (!sr && st == 0u && c.tt1 < we) {
+        const uint64_t t1 = c.tt1;
+        dr = t1 < c.tt0 && t1 < c.tt2 && t1 < c.dt && t1 < ht && c.cq_count == 0 && c.tq_count == 0;
+    }
+    if (dr) {
+        c.now = c.tt1; c.tt1 = kInf; c.c_events++;
+        c.q_seq = c.ts1; c.q_src = c.h; c.q_sub = 0;
+        c.w_msgs = 0; c.w_fl = 0;
+        refill_fast(P, c);
+    }
     return true;
 }
 

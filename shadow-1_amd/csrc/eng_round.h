@@ -1261,7 +1261,14 @@ __device__ __forceinline__ uint64_t cal_lower_bound_sp(const DParams& P, const u
 struct PsNoFin {
     __device__ __forceinline__ void operator()() const {}
 };
-template <bool PF, bool XCH = true, class Fin = PsNoFin>
+// STEADY (the lean k_round_ps): the steady iteration (steady_iter, eng_device.h)
+// ahead of the general one, which the lanes it does not take run unchanged.
+// SHD_TIMING_NOLOOP: the timing build without the clock reads inside the loop
+// (the stamps and the iteration count stay), for the product's cost per iteration.
+#if defined(SHD_TIMING_LIGHT) && !defined(SHD_TIMING_NOLOOP)
+#define SHD_TIMING_INLOOP 1
+#endif
+template <bool PF, bool XCH = true, class Fin = PsNoFin, bool STEADY = false>
 __device__ __forceinline__ void ps_loop_close(const DParams& P, HostCtx& c, bool active, bool has, const PsRsrc& R,
                                               uint32_t lb, uint64_t we, uint32_t (&w)[kNBW], uint32_t clr_p,
                                               uint32_t clr, uint64_t& next, PfBins* pb, uint64_t* span,
@@ -1279,27 +1286,31 @@ __device__ __forceinline__ void ps_loop_close(const DParams& P, HostCtx& c, bool
             for (;;) {
 #ifdef SHD_TIMING_LIGHT
                 n_it++;
+#endif
+#ifdef SHD_TIMING_INLOOP
                 ta = wall_clock64();
 #endif
-                if (st == 0u) {
+                bool sdy = false;
+                if (STEADY) sdy = steady_iter(P, c, we, st);
+                if (st == 0u && !sdy) {
                     shd_event e;
-#ifdef SHD_TIMING_LIGHT
+#ifdef SHD_TIMING_INLOOP
                     const unsigned long long q0 = wall_clock64();
 #endif
                     const bool got = take_next(P, c, we, e);
-#ifdef SHD_TIMING_LIGHT
+#ifdef SHD_TIMING_INLOOP
                     const unsigned long long q1 = wall_clock64();
                     t_q[0] += q1 - q0;
 #endif
                     if (got) {
                         c.now = e.time;
                         begin_event(P, c, e);
-#ifdef SHD_TIMING_LIGHT
+#ifdef SHD_TIMING_INLOOP
                         t_q[1] += wall_clock64() - q1;
 #endif
                         st = ((c.w_fl & ~W_READ) | c.w_msgs) ? 1u : 0u;
 #ifndef SHD_NO_FUSE
-#ifdef SHD_TIMING_LIGHT
+#ifdef SHD_TIMING_INLOOP
                         const unsigned long long q2 = wall_clock64();
 #endif
                         if (st == 0u && c.tt2 < we) {   // the notification, when it is next (round_body)
@@ -1312,7 +1323,7 @@ __device__ __forceinline__ void ps_loop_close(const DParams& P, HostCtx& c, bool
                                 st = c.w_fl ? 1u : 0u;
                             }
                         }
-#ifdef SHD_TIMING_LIGHT
+#ifdef SHD_TIMING_INLOOP
                         t_q[2] += wall_clock64() - q2;
 #endif
                         if (st == 0u && c.tt1 < we) {   // the periodic refill, when it is next
@@ -1329,7 +1340,7 @@ __device__ __forceinline__ void ps_loop_close(const DParams& P, HostCtx& c, bool
                         st = 3u;
                     }
                 }
-#ifdef SHD_TIMING_LIGHT
+#ifdef SHD_TIMING_INLOOP
                 {
                     const unsigned long long tb = wall_clock64();
                     t_take += tb - ta;
@@ -1337,7 +1348,7 @@ __device__ __forceinline__ void ps_loop_close(const DParams& P, HostCtx& c, bool
                 }
 #endif
                 if (st == 1u) st = run_work(P, c) ? 0u : 2u;
-#ifdef SHD_TIMING_LIGHT
+#ifdef SHD_TIMING_INLOOP
                 t_work += wall_clock64() - ta;
 #endif
                 if (__ballot(st <= 1u) == 0) break;
@@ -1348,6 +1359,8 @@ __device__ __forceinline__ void ps_loop_close(const DParams& P, HostCtx& c, bool
 #endif
 #ifdef SHD_TIMING_LIGHT
             n_fl++;
+#endif
+#ifdef SHD_TIMING_INLOOP
             ta = wall_clock64();
 #endif
             // PF: the round's last flush, when it is one batch, is taken below,
@@ -1359,7 +1372,7 @@ __device__ __forceinline__ void ps_loop_close(const DParams& P, HostCtx& c, bool
                 total = 0;
             }
             flush_wave<true, XCH>(P, c, !PF && last, pd);
-#ifdef SHD_TIMING_LIGHT
+#ifdef SHD_TIMING_INLOOP
             if (!last) t_fl += wall_clock64() - ta;
 #endif
             if (last) break;
@@ -1611,6 +1624,12 @@ constexpr bool kPsPf = true;
 constexpr bool kPsPf = false;
 #endif
 
+#ifndef SHD_NO_STEADY
+constexpr bool kPsSteady = true;
+#else
+constexpr bool kPsSteady = false;
+#endif
+
 template <bool LEAN>
 __global__ __launch_bounds__(kBlock) void k_round_ps(uint64_t window, int nb, DevSummary* __restrict__ ring,
                                                       const DevCtl* __restrict__ ctl, PsShare* __restrict__ shares,
@@ -1716,8 +1735,9 @@ __global__ __launch_bounds__(kBlock) void k_round_ps(uint64_t window, int nb, De
             nev = wave_sum_u32(c.c_events);
             npkt = wave_sum_u32(c.c_pkt);
         };
-        ps_loop_close<kPsPf, false>(P, c, active, has, R, lb, we, w, (uint32_t)(ws >> P.bin_shift) & (kNB - 1), clr, next, &pb,
-                                    &span, fin);
+        ps_loop_close<kPsPf, false, decltype(fin), LEAN && kPsSteady>(P, c, active, has, R, lb, we, w,
+                                                                      (uint32_t)(ws >> P.bin_shift) & (kNB - 1), clr, next, &pb,
+                                                                      &span, fin);
         acc[2] += c.c_sent; acc[3] += c.c_idrop;
         const uint32_t pend = c.n_pend ? kPsPend : 0u;
         const uint32_t fl = wave_or_u32(c.err | pend);
