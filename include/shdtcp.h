@@ -132,7 +132,12 @@ typedef struct shd_tcp_model {
     const int32_t* app_peer;
     const double* dest_cum;
     const uint8_t* host_class;
-    int32_t n_classes, _pad2;
+    int32_t n_classes;
+    /* SHD_TCP_OPT_SERIES: records of the engine's sample array (<= 0: the
+     * default, the larger of 2^20 and four per socket slot of the engine's
+     * hosts; at most 2^26, more is refused with -22).  96 bytes each.  It must
+     * hold what the hosts append between two drains (series_interval_us). */
+    int32_t series_cap;
     /* Packet capture (the reference's <host logpcap="true">,
      * network_interface.c:337-373): pcap_host[h] != 0 makes host h a capture
      * host; NULL: none.  A capture host's lane writes one shd_pcap_rec for
@@ -150,7 +155,27 @@ typedef struct shd_tcp_model {
      * datagram (network_interface.c:348, packet.c:485-489): a model with a
      * capture host and a datagram process is refused (-22). */
     const uint8_t* pcap_host;
-    uint32_t pcap_ring, _pad10;
+    uint32_t pcap_ring;
+    /* SHD_TCP_OPT_SERIES: the sampling interval I in microseconds (I = 1000 *
+     * series_interval_us ns; nonzero with the option, ignored without).  The
+     * boundaries are T_k = k * I, k >= 1, T_k < end_time.  A flow record is
+     * touched when one of the six statuses its counters count is attributed to
+     * it (shd_tcp_flow: SND_CREATED, SND_TCP_RETRANSMITTED, INET_DROPPED,
+     * RCV_SOCKET_DELIVERED, RCV_SOCKET_DROPPED, ROUTER_DROPPED; setting
+     * t_established does not count).  A touched record yields one
+     * shd_tcp_sample labelled with the first boundary after the touch -- an
+     * event at exactly T_k belongs to the interval after it -- holding the
+     * record's cumulative counters after every event of its host before that
+     * boundary.  An interval without a touch yields no sample: the series is
+     * sparse and its reader fills forward.  A last touch whose boundary is not
+     * before end_time yields none either: the flow record is the end state.
+     * The owning host's lane appends the samples to one engine-wide array in
+     * device memory (series_cap), which is emptied into host memory where the
+     * capture rings are (shd_tcp_run: after every batch of 64 rounds; a group:
+     * after 64 rounds at the latest, or once the array is past half), so a
+     * series is as long as the run; an append that finds the array full sets
+     * SHD_TCP_ERR_SERIES and writes nothing. */
+    uint32_t series_interval_us;
     /* The bootstrap period (<shadow bootstraptime>, shd_model.bootstrap_end):
      * ns, 0 for none.  worker_isBootstrapActive() is now < bootstrap_end
      * (worker.c:462-466: strict, at the executing event's time), read once
@@ -327,6 +352,30 @@ typedef struct shd_tcp_flow {
     int32_t srtt, rttvar;
 } shd_tcp_flow;
 
+/* One sample of a run with SHD_TCP_OPT_SERIES (shd_tcp_model.
+ * series_interval_us states the rule): flow record `flow` of the same result
+ * (shd_tcp_result_flows' index) as it stood at boundary t -- the seven
+ * counters of shd_tcp_flow, pinned by a traced run's [STATUS] lines
+ * (tests/tcp_series_expect.py), and the socket's state, cwnd, ssthresh, srtt
+ * and rttvar when the sample was taken (by the host's first event at or past
+ * t, or at the end of the run), which are the device's own as in shd_tcp_flow. */
+typedef struct shd_tcp_sample {
+    uint64_t t;                 /* the boundary T_k, ns */
+    uint32_t flow;              /* index into shd_tcp_result_flows' array of the same result */
+    int32_t  host;
+    uint64_t bytes_delivered, packets_created, bytes_created;
+    uint64_t retransmitted, inet_dropped, socket_dropped, router_dropped;
+    uint32_t cwnd, ssthresh; int32_t srtt, rttvar;   /* the socket's values when the sample was taken */
+    uint8_t  state, _pad[7];
+} shd_tcp_sample;
+
+/* what the drains of a run's sample array saw: the times it was emptied with
+ * something in it, the most records one drain found, and its capacity */
+typedef struct shd_tcp_series_info {
+    uint64_t drains;
+    uint32_t peak, capacity;
+} shd_tcp_series_info;
+
 /* One ordered vertex pair of a run with SHD_TCP_OPT_PATHS: what the hosts on
  * v_src handed to worker_sendPacket for hosts on v_dst (worker.c:260-321),
  * counted where the reference raises the packet's status, so every counted
@@ -347,8 +396,10 @@ typedef struct shd_tcp_path {
                                       pair, either outcome; a record exists only for a pair that saw one */
 } shd_tcp_path;
 
-/* shd_tcp_model.options: independent bits */
-enum { SHD_TCP_OPT_FLOWS = 1, SHD_TCP_OPT_PATHS = 2 };
+/* shd_tcp_model.options: independent bits, but SHD_TCP_OPT_SERIES is valid only
+ * together with SHD_TCP_OPT_FLOWS and a nonzero series_interval_us (-22
+ * otherwise, before any device call) */
+enum { SHD_TCP_OPT_FLOWS = 1, SHD_TCP_OPT_PATHS = 2, SHD_TCP_OPT_SERIES = 4 };
 
 /* The most entries the device's pair table gets (SHD_TCP_OPT_PATHS; 64 bytes
  * each: 256 MiB).  Its capacity is a power of two at least twice min(Vu^2, E +
@@ -377,8 +428,10 @@ enum {
     SHD_TCP_ERR_MAILBOX = 16, SHD_TCP_ERR_TRACE = 32, SHD_TCP_ERR_SACK = 64, SHD_TCP_ERR_INTERNAL = 128,
     SHD_TCP_ERR_QLOG = 256, SHD_TCP_ERR_FIRST_TOUCH = 512,
     SHD_TCP_ERR_PCAP = 1024,  /* a capture ring filled between two drains (pcap_ring) */
-    SHD_TCP_ERR_PATHS = 2048  /* the device's pair table had no free entry for a vertex pair (SHD_TCP_OPT_PATHS):
+    SHD_TCP_ERR_PATHS = 2048, /* the device's pair table had no free entry for a vertex pair (SHD_TCP_OPT_PATHS):
                                  counts could not be placed, the path records are incomplete */
+    SHD_TCP_ERR_SERIES = 4096 /* the sample array filled between two drains (SHD_TCP_OPT_SERIES, series_cap):
+                                 the sample was not written, the series is incomplete */
 };
 
 /* Run the model to end_time on the current HIP device (the reference's
@@ -426,6 +479,20 @@ int shd_tcp_result_flows(const shd_tcp_result* r, const shd_tcp_flow** recs, uin
  * hosts' sends to its own cache, as shd_eng_path_counts documents for engine
  * groups. */
 int shd_tcp_result_paths(const shd_tcp_result* r, const shd_tcp_path** recs, uint64_t* n);
+
+/* The samples of the hosts this result covers (a result of shd_tcp_run /
+ * shd_tcp_run_group only), sorted by (flow, t): `flow` indexes the array
+ * shd_tcp_result_flows gives for the same result, so a group's rank returns
+ * its own hosts' samples against its own flow array (the ranks concatenated
+ * in rank order, each rank's `flow` offset by the records before it, are the
+ * one-engine array).  info, when not NULL, takes the drains' figures.  *recs
+ * NULL and *n 0 (info zero) when the model did not set SHD_TCP_OPT_SERIES.
+ * Owned by the result.  Returns 0, -22 for a NULL r, recs or n.  Without the
+ * option a run allocates nothing for the series, launches nothing extra and
+ * the round's event loop tests one launch-uniform word; a rerun from the
+ * start (first_touch_reruns) starts the series again with the records. */
+int shd_tcp_result_series(const shd_tcp_result* r, const shd_tcp_sample** recs, uint64_t* n,
+                          shd_tcp_series_info* info);
 
 /* The same model on a group of engines, one per process and GPU (shdgpu.h
  * shd_comm: RCCL, or the host-memory transport for several processes on one

@@ -37,7 +37,11 @@
 // SHD_TCP_OPT_PATHS the packets worker_send_packet sent and dropped are
 // counted per vertex pair: an accumulator beside each socket slot (DPath,
 // path_status), folded into a pair table in device memory (PEnt, path_add) and
-// compacted into shd_tcp_path records at the end (k_tcp_path_*).
+// compacted into shd_tcp_path records at the end (k_tcp_path_*).  With
+// SHD_TCP_OPT_SERIES the flow records a host touched are sampled where its
+// lane crosses an interval boundary (series_cross, series_take) into one
+// engine-wide array that the host empties between batches of rounds
+// (series_drain), and what is still touched at the end by k_tcp_series_flush.
 //
 // The work is branchy per-host control flow with a few events per host and
 // round: latency-bound by design ("TCP"); it shares nothing with
@@ -296,9 +300,10 @@ struct DFlow {
     uint64_t retransmitted, inet_dropped, socket_dropped, router_dropped;
     uint32_t local_ip, peer_ip;
     uint16_t local_port, peer_port;
-    uint32_t role;
+    uint32_t role;   // bit 0: shd_tcp_flow's role; kFlowTouched: counted since its last sample (flow time series)
 };
 static_assert(sizeof(DFlow) == 104, "a flow record beside each socket slot");
+constexpr uint32_t kFlowTouched = 1u << 31;
 // A socket slot's path accumulator (shd_tcp_model.options & SHD_TCP_OPT_PATHS):
 // Glob::pacc, one per slot beside the socket, not in it: what the slot's
 // packets added to the record of its current vertex pair (va, vb: Glob::hv's
@@ -454,6 +459,16 @@ struct Glob {
     PEnt* ptab;
     uint32_t* pt_full;
     uint32_t pt_mask, path_on;
+    // flow time series (SHD_TCP_OPT_SERIES, with flow records only): ser_on is
+    // the one launch-uniform word the round's event loop tests; the engine-wide
+    // sample array ser [ser_cap] and its append counter *nser (emptied between
+    // batches of rounds: series_drain), each local host's next boundary
+    // ser_next [nloc] and the interval in ns.  All null / 0 without the option.
+    uint32_t ser_on, ser_cap;
+    shd_tcp_sample* ser;
+    uint32_t* nser;
+    uint64_t* ser_next;
+    uint64_t ser_ival;
 };
 struct XSegHead { uint32_t n, nsack, err, _pad[13]; };   // 64 B, then xcap Mails, then xsack_cap SACK words
 static_assert(sizeof(XSegHead) == 64, "segment header");
@@ -798,32 +813,42 @@ __device__ void flow_status(L& c, const DSock* k, const DPkt* p, uint8_t st) {
         f->packets_created++;
         f->bytes_created += p->len;
         if ((p->flags & F_FIN) && !f->t_fin) f->t_fin = c.now;
-        return;
+        break;
     case S_SND_TCP_RETRANSMITTED:   // tcp.c:1060
-        if (k) flow_of(c, k)->retransmitted++;
-        return;
+        if (!k) return;
+        f = flow_of(c, k);
+        f->retransmitted++;
+        break;
     case S_INET_DROPPED:   // worker.c:281-290, the sending socket in hand
-        if (k && !k->udp) flow_of(c, k)->inet_dropped++;
-        return;
+        if (!k || k->udp) return;
+        f = flow_of(c, k);
+        f->inet_dropped++;
+        break;
     case S_RCV_SOCKET_DELIVERED:   // tcp.c:2226, 2266
         if (!k) return;
         f = flow_of(c, k);
         f->t_last_delivered = c.now;
         f->bytes_delivered += p->len;
-        return;
+        break;
     case S_RCV_SOCKET_DROPPED:   // while socket k processed the packet (tcp.c:1597-1660, 1777-2099): a
                                  // listener that found no child for it has no record of its own
         if (!k) return;
         f = k->server ? flow_addressed(c, p) : flow_of(c, k);
-        if (f) f->socket_dropped++;
-        return;
+        if (!f) return;
+        f->socket_dropped++;
+        break;
     case S_ROUTER_DROPPED:   // at this host's router (router_queue_codel.c's drop): no socket in hand
         f = flow_addressed(c, p);
-        if (f) f->router_dropped++;
-        return;
+        if (!f) return;
+        f->router_dropped++;
+        break;
     default:
         return;
     }
+    // one of the six counted statuses went to f: its next boundary samples it
+    // (series_take; the bit is read by nothing else and masked where the
+    // record is gathered)
+    f->role |= kFlowTouched;
 }
 
 // ------------------------------------------------------------ path records (shd_tcp_path)
@@ -3111,10 +3136,12 @@ __global__ void __launch_bounds__(kFlowScan) k_tcp_flow_scan(const uint32_t* __r
     for (int32_t i = a; i < b; i++) { off[i] = base; base += cnt[i]; }
     if (t == kFlowScan - 1) off[n] = part[t];
 }
+// smap (the flow time series' only): each slot's index among the records, ~0: none
 __global__ void k_tcp_flow_write(Glob g, const uint32_t* __restrict__ off, shd_tcp_flow* __restrict__ out,
-                                 int32_t ns) {   // one thread per socket slot
+                                 int32_t ns, uint32_t* __restrict__ smap) {   // one thread per socket slot
     const int32_t s = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
     if (s >= ns) return;
+    if (smap) smap[s] = ~0u;
     const DFlow f = g.flow[s];
     if (!f.packets_created) return;
     const DSock* k = &g.sock[s];
@@ -3137,13 +3164,14 @@ __global__ void k_tcp_flow_write(Glob g, const uint32_t* __restrict__ off, shd_t
         }
     }
     r.local_ip = f.local_ip; r.peer_ip = f.peer_ip; r.local_port = f.local_port; r.peer_port = f.peer_port;
-    r.role = (uint8_t)f.role; r.state = (uint8_t)k->state; r._pad = 0;
+    r.role = (uint8_t)(f.role & 1u); r.state = (uint8_t)k->state; r._pad = 0;
     r.t_open = f.t_open; r.t_established = f.t_established; r.t_last_delivered = f.t_last_delivered; r.t_fin = f.t_fin;
     r.bytes_delivered = f.bytes_delivered; r.packets_created = f.packets_created; r.bytes_created = f.bytes_created;
     r.retransmitted = f.retransmitted; r.inet_dropped = f.inet_dropped; r.socket_dropped = f.socket_dropped;
     r.router_dropped = f.router_dropped;
     r.cwnd = k->cwnd; r.ssthresh = k->reno_ssthresh; r.srtt = k->srtt; r.rttvar = k->rttvar;
     out[at] = r;
+    if (smap) smap[s] = at;
 }
 
 // The run's path records at its end (SHD_TCP_OPT_PATHS): the table's entries
@@ -3205,6 +3233,68 @@ __device__ bool ingest_mail(L& c, int32_t s) {
     return true;
 }
 
+// ------------------------------------------------------------ flow time series (shd_tcp_sample)
+// Host h's touched records sampled at boundary t: one record appended to the
+// engine's array for each (its place taken with an atomic add: hosts sit in
+// different waves and blocks), the bit cleared.  `flow` holds the slot; the
+// host side names the record once the run's records are gathered.  An append
+// past the capacity writes nothing and returns the error bit for the host.
+__device__ uint32_t series_take(const Glob& g, int32_t h, uint64_t t) {
+    uint32_t err = 0;
+    const int32_t s1 = g.sock_off[h + 1];
+    for (int32_t s = g.sock_off[h]; s < s1; s++) {
+        DFlow* f = &g.flow[s];
+        const uint32_t role = f->role;
+        if (!(role & kFlowTouched)) continue;
+        f->role = role & ~kFlowTouched;
+        if (!f->packets_created) continue;   // (no record: a status counts only from the first packet on)
+        const uint32_t at = atomicAdd(g.nser, 1u);
+        if (at >= g.ser_cap) { err |= SHD_TCP_ERR_SERIES; continue; }
+        const DSock* k = &g.sock[s];
+        shd_tcp_sample r;
+        r.t = t; r.flow = (uint32_t)s; r.host = g.h0 + h;
+        r.bytes_delivered = f->bytes_delivered; r.packets_created = f->packets_created;
+        r.bytes_created = f->bytes_created; r.retransmitted = f->retransmitted; r.inet_dropped = f->inet_dropped;
+        r.socket_dropped = f->socket_dropped; r.router_dropped = f->router_dropped;
+        r.cwnd = k->cwnd; r.ssthresh = k->reno_ssthresh; r.srtt = k->srtt; r.rttvar = k->rttvar;
+        r.state = (uint8_t)k->state;
+        for (int i = 0; i < 7; i++) r._pad[i] = 0;
+        g.ser[at] = r;
+    }
+    return err;
+}
+// how far host h's lane runs before it has to look at its boundary: the
+// window's end, or the boundary when that comes first
+__device__ __noinline__ uint64_t series_limit(const Glob& g, int32_t h, uint64_t wend) {
+    const uint64_t nb = g.ser_next[h];
+    return nb < wend ? nb : wend;
+}
+// the lane's next event, at time t, lies at or past the host's boundary (and
+// in the window): the touched records are sampled with that boundary's label,
+// and the next boundary is the first one after t -- an event at a boundary
+// opens the interval after it.  Returns the lane's new limit.
+__device__ __noinline__ uint64_t series_cross(L& c, uint64_t t, uint64_t wend) {
+    const Glob& g = *c.g;
+    c.H->err |= series_take(g, c.h, g.ser_next[c.h]);
+    const uint64_t nb = (t / g.ser_ival + 1) * g.ser_ival;
+    g.ser_next[c.h] = nb;
+    return nb < wend ? nb : wend;
+}
+// the end of the run: what is still touched, when its boundary lies before
+// the end (one thread per host; the flow record itself is the end state)
+__global__ void k_tcp_series_flush(Glob g) {
+    const int32_t h = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (h >= g.nloc) return;
+    const uint64_t nb = g.ser_next[h];
+    if (nb >= g.end_time) return;
+    const uint32_t err = series_take(g, h, nb);
+    if (err) g.host[h].err |= err;
+}
+__global__ void k_tcp_series_init(uint64_t* __restrict__ next, int32_t n, uint64_t ival) {
+    const int32_t h = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (h < n) next[h] = ival;
+}
+
 // one conservative round: the mailbox's deliveries for this host, then every
 // event before the window's end
 __global__ void __launch_bounds__(64) k_tcp_round(Glob g) {
@@ -3254,15 +3344,31 @@ __global__ void __launch_bounds__(64) k_tcp_round(Glob g) {
         if (!ingest_mail(c, s)) break;
     TCP_PROF(0);
     uint64_t nev = 0;
-    while (c.H->nev && evq_base(&gl, h)[0].time < wend && !c.H->err) {
-        const DEv e = evq_pop(c);
-        TCP_PROF(1);
-        c.now = e.time;
-        c.active = h;
-        c.ksrc = e.src; c.kseq = e.seq; c.kq = 0;
-        execute(c, e);
-        TCP_PROF(2 + (e.kind < 12 ? e.kind : 12));
-        if (++nev > (1u << 24)) c.H->err |= SHD_TCP_ERR_INTERNAL;   // a runaway round: stop, report
+    // The flow time series costs the event loop nothing per event: the lane
+    // runs its events up to `lim`, the window's end or, with the series, its
+    // host's next boundary when that comes first; there the touched records
+    // are sampled and the loop goes on to the next limit (series_cross).
+    // Without the option lim is wend and the outer loop runs once: one test of
+    // a launch-uniform word before the events, none among them.  Every counted
+    // status is raised in execute, with c.now the event's time.
+    uint64_t lim = wend;
+    if (gl.ser_on) lim = series_limit(gl, h, wend);
+    for (;;) {
+        while (c.H->nev && evq_base(&gl, h)[0].time < lim && !c.H->err) {
+            const DEv e = evq_pop(c);
+            TCP_PROF(1);
+            c.now = e.time;
+            c.active = h;
+            c.ksrc = e.src; c.kseq = e.seq; c.kq = 0;
+            execute(c, e);
+            TCP_PROF(2 + (e.kind < 12 ? e.kind : 12));
+            if (++nev > (1u << 24)) c.H->err |= SHD_TCP_ERR_INTERNAL;   // a runaway round: stop, report
+        }
+        if (lim == wend) break;   // (without the series: always)
+        if (!c.H->nev || c.H->err) break;
+        const uint64_t t = evq_base(&gl, h)[0].time;
+        if (t >= wend) break;   // the boundary is some later round's event's
+        lim = series_cross(c, t, wend);
     }
 #ifdef SHD_TCP_PROF
     {
@@ -3572,7 +3678,7 @@ enum WsSlot {
     kWsAppSpec, kWsAppPeer, kWsDestCum, kWsHostClass, kWsIpAll, kWsBwu, kWsBwd, kWsProcPort, kWsPortNew, kWsXsend,
     kWsXrecv, kWsPmine, kWsPall, kWsXcnt, kWsGmine, kWsGall, kWsPcap, kWsNpcap, kWsPcapSlot, kWsHostHb, kWsSockOff, kWsDir, kWsIfq,
     kWsProcOff, kWsFlow, kWsFlowCnt, kWsFlowOff, kWsFlowOut, kWsPacc, kWsPtab, kWsPtFull, kWsPtCnt, kWsPtOff,
-    kWsPtOut, kWsSlots
+    kWsPtOut, kWsSer, kWsNser, kWsSerNext, kWsSerMap, kWsSlots
 };
 // what the library allocates for a result: the public struct first (its size
 // is pinned), then the flow records shd_tcp_result_flows and the path records
@@ -3583,6 +3689,9 @@ struct TcpResultX {
     uint64_t n_flows;
     shd_tcp_path* paths;
     uint64_t n_paths;
+    shd_tcp_sample* series;   // shd_tcp_result_series: sorted by (flow, t)
+    uint64_t n_series;
+    shd_tcp_series_info series_info;
 };
 // The pair table's capacity (shdtcp.h): a power of two at least twice the
 // most ordered vertex pairs the model's hosts can send over -- min(Vu^2, E + 2
@@ -3721,6 +3830,43 @@ static hipError_t pcap_drain(TcpPcap& pc, const Glob& g, hipStream_t st) {
     return hipStreamSynchronize(st);
 }
 
+// the flow time series on the host side (SHD_TCP_OPT_SERIES): the samples so
+// far in append order, grown by the drains.  A rerun from the start (TcpSched)
+// is a new call of tcp_run_impl and starts empty.
+constexpr uint32_t kSeriesCapMin = 1u << 20;   // the sample array's default capacity: this, or kSeriesPerSlot
+constexpr uint32_t kSeriesPerSlot = 4;         // records per socket slot when that is more
+constexpr uint32_t kSeriesCapMax = 1u << 26;
+struct TcpSeries {
+    std::vector<shd_tcp_sample> recs;
+    uint32_t cnt = 0;   // the append counter as last copied
+    uint64_t drains = 0, rounds_since = 0;
+    uint32_t peak = 0;
+    double drain_ms = 0;   // host wall time of the drains (SHD_TCP_SERIES_TIMING prints it)
+};
+// the array's used part (sr.cnt: the counter just copied; past the capacity
+// nothing was written) to host memory and the counter back to zero, on the
+// run's stream: the array never carries samples from one drain to the next
+static hipError_t series_drain(TcpSeries& sr, const Glob& g, hipStream_t st) {
+    sr.rounds_since = 0;
+    const uint32_t n = std::min(sr.cnt, g.ser_cap);
+    if (!sr.cnt) return hipSuccess;
+    const auto t0 = std::chrono::steady_clock::now();
+    sr.cnt = 0;
+    if (n) {
+        sr.drains++;
+        sr.peak = std::max(sr.peak, n);
+        const size_t at = sr.recs.size();
+        sr.recs.resize(at + n);
+        const hipError_t e = hipMemcpyAsync(sr.recs.data() + at, g.ser, sizeof(shd_tcp_sample) * n, hipMemcpyDeviceToHost, st);
+        if (e != hipSuccess) return e;
+    }
+    hipError_t e = hipMemsetAsync(g.nser, 0, sizeof(uint32_t), st);
+    if (e != hipSuccess) return e;
+    e = hipStreamSynchronize(st);
+    sr.drain_ms += ms_since(t0);
+    return e;
+}
+
 // The socket slots and processes of hosts [h0, h0 + nloc) as ranges: host
 // h0 + i's slots are [so[i], so[i + 1]), its processes hp[po[i] .. po[i + 1])
 // in <process> order.  A host's slots are the sockets it can ever create (a
@@ -3773,6 +3919,10 @@ static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, s
     if (!m || !out || m->n_hosts <= 0 || m->n_hosts > (1 << 26) || m->n_procs < 0 || !m->host_ip || !m->host_seed || !m->bw_down_kibps ||
         !m->bw_up_kibps || (!pc && (!m->path_lat_ms || !m->path_rel || m->n_vertices <= 0)) || !m->host_vertex ||
         (m->n_procs && (!m->proc_host || !m->proc_start || !m->proc_peer)))
+        return -22;
+    // the flow time series samples flow records at an interval: the bit needs both
+    if ((m->options & SHD_TCP_OPT_SERIES) &&
+        (!(m->options & SHD_TCP_OPT_FLOWS) || !m->series_interval_us || m->series_cap > (int32_t)kSeriesCapMax))
         return -22;
     // path_cache mode: a built cache of an undirected graph (the directed
     // lookup reruns rows, topology.c:1987-1990: not restated on the device)
@@ -3909,6 +4059,9 @@ static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, s
     const bool paths_on = (m->options & SHD_TCP_OPT_PATHS) != 0;
     uint32_t* d_pcnt = nullptr; uint32_t* d_poff = nullptr;
     uint32_t pt_cap = 0;
+    const bool series_on = (m->options & SHD_TCP_OPT_SERIES) != 0;
+    TcpSeries ser;
+    uint32_t* d_smap = nullptr;
     double* d_lat = nullptr; double* d_rel = nullptr;
     uint32_t* d_spec = nullptr; int32_t* d_apeer = nullptr; double* d_cum = nullptr; uint8_t* d_cls = nullptr;
     int32_t* d_hv = nullptr;
@@ -4111,6 +4264,26 @@ static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, s
             g.flow_on = 1;
             g.stat_on |= 2u;
         }
+        if (series_on) {   // the engine's sample array and its counter, a boundary per host, the gather's slot map
+            g.ser_cap = m->series_cap > 0 ? (uint32_t)m->series_cap
+                                          : (uint32_t)std::min<uint64_t>(std::max<uint64_t>(kSeriesCapMin, kSeriesPerSlot * (uint64_t)ns),
+                                                                         kSeriesCapMax);
+            g.ser_ival = 1000ull * m->series_interval_us;
+            if (ws_alloc(ws, kWsSer, &g.ser, sizeof(shd_tcp_sample) * (size_t)g.ser_cap) != hipSuccess ||
+                ws_alloc(ws, kWsNser, &g.nser, sizeof(uint32_t)) != hipSuccess ||
+                ws_alloc(ws, kWsSerNext, &g.ser_next, sizeof(uint64_t) * (size_t)nloc) != hipSuccess ||
+                ws_alloc(ws, kWsSerMap, &d_smap, sizeof(uint32_t) * ns) != hipSuccess) {
+                (void)hipGetLastError();
+                fprintf(stderr, "shd_tcp_run: no device memory for the flow time series (%u samples, %.1f GB); "
+                                "set a smaller series_cap\n", g.ser_cap, sizeof(shd_tcp_sample) * (double)g.ser_cap / 1e9);
+                rc = -12;
+                goto done;
+            }
+            HCHECK(hipMemset(g.nser, 0, sizeof(uint32_t)));
+            k_tcp_series_init<<<(unsigned)((nloc + 255) / 256), 256>>>(g.ser_next, nloc, g.ser_ival);
+            HCHECK(hipGetLastError());
+            g.ser_on = 1;
+        }
         if (paths_on) {   // an accumulator beside every slot, the pair table, and the gather's flags and offsets
             pt_cap = tcp_path_slots(m, hvi);
             if (ws_alloc(ws, kWsPacc, &g.pacc, sizeof(DPath) * ns) != hipSuccess ||
@@ -4286,8 +4459,11 @@ static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, s
                 if (g.pcap_on)   // the batch's captures: the counts with the control word, then the rings' used parts
                     HCHECK(hipMemcpyAsync(pcp.cnt.data(), g.npcap, sizeof(uint32_t) * pcp.cnt.size(),
                                           hipMemcpyDeviceToHost, st));
+                if (g.ser_on)    // the batch's samples: the counter with the control word, then the array's used part
+                    HCHECK(hipMemcpyAsync(&ser.cnt, g.nser, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
                 HCHECK(hipStreamSynchronize(st));
                 if (g.pcap_on) HCHECK(pcap_drain(pcp, g, st));
+                if (g.ser_on) HCHECK(series_drain(ser, g, st));
             } else {
                 // a group's round (slave.c:437-462 across engines): the earliest
                 // event over the group opens the window; the round's ports and
@@ -4391,12 +4567,15 @@ static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, s
                 if (g.pcap_on)
                     HCHECK(hipMemcpyAsync(pcp.cnt.data(), g.npcap, sizeof(uint32_t) * pcp.cnt.size(),
                                           hipMemcpyDeviceToHost, st));
+                if (g.ser_on) HCHECK(hipMemcpyAsync(&ser.cnt, g.nser, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
                 HCHECK(hipStreamSynchronize(st));
                 if (g.pcap_on) {   // a drain every 64 rounds at the latest, or once a ring is past half
                     bool due = ++pcp.rounds_since >= 64;
                     for (uint32_t n : pcp.cnt) due |= n > g.pcap_ring / 2;
                     if (due) HCHECK(pcap_drain(pcp, g, st));
                 }
+                if (g.ser_on && (++ser.rounds_since >= 64 || ser.cnt > g.ser_cap / 2))   // the sample array alike
+                    HCHECK(series_drain(ser, g, st));
             }
             if (hctl.halted) break;
             if (hctl.rounds > (1ull << 26)) { res->error |= SHD_TCP_ERR_INTERNAL; break; }
@@ -4406,6 +4585,13 @@ static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, s
             HCHECK(hipMemcpyAsync(pcp.cnt.data(), g.npcap, sizeof(uint32_t) * pcp.cnt.size(), hipMemcpyDeviceToHost, st));
             HCHECK(hipStreamSynchronize(st));
             HCHECK(pcap_drain(pcp, g, st));
+        }
+        if (g.ser_on) {   // the records still touched (k_tcp_series_flush), with what the array holds since the last drain
+            k_tcp_series_flush<<<(unsigned)((nloc + 255) / 256), 256, 0, st>>>(g);
+            HCHECK(hipGetLastError());
+            HCHECK(hipMemcpyAsync(&ser.cnt, g.nser, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            HCHECK(hipStreamSynchronize(st));
+            HCHECK(series_drain(ser, g, st));
         }
         HCHECK(hipEventRecord(e1, st));
         HCHECK(hipEventSynchronize(e1));
@@ -4461,7 +4647,7 @@ static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, s
         resx->n_flows = nf;
         if (nf) {
             HCHECK(ws_alloc(ws, kWsFlowOut, &d_out, sizeof(shd_tcp_flow) * nf));
-            k_tcp_flow_write<<<(unsigned)((ns + 255) / 256), 256, 0, st>>>(g, d_foff, d_out, ns);
+            k_tcp_flow_write<<<(unsigned)((ns + 255) / 256), 256, 0, st>>>(g, d_foff, d_out, ns, d_smap);
             HCHECK(hipGetLastError());
             HCHECK(hipMemcpyAsync(resx->flows, d_out, sizeof(shd_tcp_flow) * nf, hipMemcpyDeviceToHost, st));
         }
@@ -4471,6 +4657,30 @@ static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, s
             float fms = 0;
             HCHECK(hipEventElapsedTime(&fms, e0, e1));
             fprintf(stderr, "shd_tcp_run: %u flow records of %d slots gathered in %.3f ms\n", nf, ns, fms);
+        }
+        if (g.ser_on) {   // the samples name their record (the gather's slot map) and come sorted by (flow, t)
+            const size_t n = ser.recs.size();
+            resx->series_info.drains = ser.drains;
+            resx->series_info.peak = ser.peak;
+            resx->series_info.capacity = g.ser_cap;
+            resx->series = (shd_tcp_sample*)malloc(sizeof(shd_tcp_sample) * (n ? n : 1));
+            if (!resx->series) { rc = -12; goto done; }
+            if (n) {
+                std::vector<uint32_t> smap((size_t)ns);
+                HCHECK(hipMemcpy(smap.data(), d_smap, sizeof(uint32_t) * (size_t)ns, hipMemcpyDeviceToHost));
+                for (shd_tcp_sample& r : ser.recs) {
+                    if (r.flow >= (uint32_t)ns || smap[r.flow] >= nf) { rc = -5; goto done; }   // (a sample of no record: never)
+                    r.flow = smap[r.flow];
+                }
+                std::sort(ser.recs.begin(), ser.recs.end(), [](const shd_tcp_sample& a, const shd_tcp_sample& b) {
+                    return a.flow != b.flow ? a.flow < b.flow : a.t < b.t;
+                });
+                memcpy(resx->series, ser.recs.data(), sizeof(shd_tcp_sample) * n);
+            }
+            resx->n_series = n;
+            if (getenv("SHD_TCP_SERIES_TIMING"))   // the drains' host wall time (copies and their waits), for measurements
+                fprintf(stderr, "shd_tcp_run: %zu samples in %llu drains (peak %u of %u), drains %.3f ms\n", n,
+                        (unsigned long long)ser.drains, ser.peak, g.ser_cap, ser.drain_ms);
         }
     }
     if (g.path_on) {   // the accumulators folded, the table compacted (k_tcp_path_*), the records named and sorted
@@ -4714,7 +4924,18 @@ extern "C" void shd_tcp_result_free(shd_tcp_result* r) {
     free(r->pcap_off);
     free(((TcpResultX*)r)->flows);   // (every result is allocated as a TcpResultX: tcp_run_impl)
     free(((TcpResultX*)r)->paths);
+    free(((TcpResultX*)r)->series);
     free(r);
+}
+
+extern "C" int shd_tcp_result_series(const shd_tcp_result* r, const shd_tcp_sample** recs, uint64_t* n,
+                                     shd_tcp_series_info* info) {
+    if (!r || !recs || !n) return -22;
+    const TcpResultX* x = (const TcpResultX*)r;
+    *recs = x->n_series ? x->series : nullptr;   // (a run with the option and no sample: NULL and 0 as well)
+    *n = x->n_series;
+    if (info) *info = x->series_info;
+    return 0;
 }
 
 extern "C" int shd_tcp_result_flows(const shd_tcp_result* r, const shd_tcp_flow** recs, uint64_t* n) {

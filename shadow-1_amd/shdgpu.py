@@ -205,8 +205,8 @@ class TcpModel(C.Structure):
                 ("options", C.c_uint32), ("path_cache", C.c_void_p),
                 ("proc_app", P(C.c_int32)), ("app_spec", P(C.c_uint32)), ("n_app_specs", C.c_int32),
                 ("udp_payload", C.c_uint32), ("app_peer", P(C.c_int32)), ("dest_cum", P(C.c_double)),
-                ("host_class", P(C.c_uint8)), ("n_classes", C.c_int32), ("_pad2", C.c_int32),
-                ("pcap_host", P(C.c_uint8)), ("pcap_ring", C.c_uint32), ("_pad10", C.c_uint32),
+                ("host_class", P(C.c_uint8)), ("n_classes", C.c_int32), ("series_cap", C.c_int32),
+                ("pcap_host", P(C.c_uint8)), ("pcap_ring", C.c_uint32), ("series_interval_us", C.c_uint32),
                 ("bootstrap_end", C.c_uint64), ("host_heartbeat", P(C.c_uint64))]
 
 
@@ -286,6 +286,33 @@ assert TCP_PATH_DTYPE.itemsize == C.sizeof(TcpPath) == 64
 TCP_PATH_SUMS = ("packets_sent", "bytes_sent", "control_sent", "packets_dropped", "bytes_dropped")
 
 
+class TcpSample(C.Structure):
+    """shd_tcp_sample (include/shdtcp.h): one flow record's counters at a boundary"""
+    _fields_ = [("t", C.c_uint64), ("flow", C.c_uint32), ("host", C.c_int32),
+                ("bytes_delivered", C.c_uint64), ("packets_created", C.c_uint64), ("bytes_created", C.c_uint64),
+                ("retransmitted", C.c_uint64), ("inet_dropped", C.c_uint64), ("socket_dropped", C.c_uint64),
+                ("router_dropped", C.c_uint64),
+                ("cwnd", C.c_uint32), ("ssthresh", C.c_uint32), ("srtt", C.c_int32), ("rttvar", C.c_int32),
+                ("state", C.c_uint8), ("_pad", C.c_uint8 * 7)]
+
+
+class TcpSeriesInfo(C.Structure):
+    """shd_tcp_series_info (include/shdtcp.h): what the drains of the sample array saw"""
+    _fields_ = [("drains", C.c_uint64), ("peak", C.c_uint32), ("capacity", C.c_uint32)]
+
+
+TCP_OPT_SERIES = 4      # SHD_TCP_OPT_SERIES (shd_tcp_model.options): per-interval samples of the flow records
+TCP_ERR_SERIES = 4096   # SHD_TCP_ERR_SERIES: the sample array filled between two drains
+# shd_tcp_sample as a structured dtype (the records shd_tcp_result_series hands out); t in ns
+TCP_SAMPLE_DTYPE = np.dtype([("t", "<u8"), ("flow", "<u4"), ("host", "<i4"),
+                             ("bytes_delivered", "<u8"), ("packets_created", "<u8"), ("bytes_created", "<u8"),
+                             ("retransmitted", "<u8"), ("inet_dropped", "<u8"), ("socket_dropped", "<u8"),
+                             ("router_dropped", "<u8"),
+                             ("cwnd", "<u4"), ("ssthresh", "<u4"), ("srtt", "<i4"), ("rttvar", "<i4"),
+                             ("state", "u1"), ("_pad", "u1", (7,))])
+assert TCP_SAMPLE_DTYPE.itemsize == C.sizeof(TcpSample) == 96
+
+
 TCP_QUERY_DTYPE = np.dtype([("time", "<u8"), ("seq", "<u8"), ("host", "<u4"), ("src", "<u4"), ("index", "<u4"),
                             ("v_src", "<i4"), ("v_dst", "<i4"), ("_pad", "<u4")])   # shd_tcp_query
 
@@ -303,6 +330,7 @@ _SIGS = {
     "shd_tcp_result_free": (None, [P(TcpResult)]),
     "shd_tcp_result_flows": (C.c_int, [P(TcpResult), P(P(TcpFlow)), P(C.c_uint64)]),
     "shd_tcp_result_paths": (C.c_int, [P(TcpResult), P(P(TcpPath)), P(C.c_uint64)]),
+    "shd_tcp_result_series": (C.c_int, [P(TcpResult), P(P(TcpSample)), P(C.c_uint64), P(TcpSeriesInfo)]),
     "shd_tcp_keep_workspace": (None, [C.c_int32]),
     "shd_pcap_format": (C.c_size_t, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int32, C.c_void_p, C.c_size_t]),
     "shd_pcap_write_host": (C.c_int, [C.c_char_p, C.c_char_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32]),
@@ -601,6 +629,77 @@ def write_paths_csv(path, recs) -> int:
         for r in a:
             out.write(",".join(str(int(r[k])) for k in TCP_PATH_DTYPE.names) + "\n")
     return len(a)
+
+
+def tcp_result_series(res):
+    """The samples of a shd_tcp_result (pointer) as a TCP_SAMPLE_DTYPE array of
+    its own, sorted by (flow, t) (shd_tcp_result_series), and the drains'
+    figures dict(drains, peak, capacity); empty and zeros when the model did
+    not set TCP_OPT_SERIES."""
+    recs, n, info = P(TcpSample)(), C.c_uint64(), TcpSeriesInfo()
+    check(lib().shd_tcp_result_series(res, C.byref(recs), C.byref(n), C.byref(info)), "shd_tcp_result_series")
+    d = dict(drains=int(info.drains), peak=int(info.peak), capacity=int(info.capacity))
+    if not n.value:
+        return np.zeros(0, dtype=TCP_SAMPLE_DTYPE), d
+    return np.frombuffer(C.string_at(recs, n.value * TCP_SAMPLE_DTYPE.itemsize), dtype=TCP_SAMPLE_DTYPE).copy(), d
+
+
+SERIES_CSV_FIELDS = tuple(k for k in TCP_SAMPLE_DTYPE.names if k != "_pad")
+
+
+def write_series_csv(path, series) -> int:
+    """Write samples (TCP_SAMPLE_DTYPE, as tcp.run(..., series_us=N) returns
+    them) as CSV: a header line (SERIES_CSV_FIELDS), then one line per sample
+    in the samples' order -- state by name (TCP_STATE_NAMES), t in ns.
+    Returns the number of samples."""
+    a = np.asarray(series, dtype=TCP_SAMPLE_DTYPE)
+    with open(path, "w") as out:
+        out.write(",".join(SERIES_CSV_FIELDS) + "\n")
+        for r in a:
+            st = int(r["state"])
+            out.write(",".join((TCP_STATE_NAMES[st] if st < len(TCP_STATE_NAMES) else str(st)) if k == "state"
+                               else str(int(r[k])) for k in SERIES_CSV_FIELDS) + "\n")
+    return len(a)
+
+
+def merge_tcp_series(pairs):
+    """The (flows, series) arrays of a group's ranks, in rank order, as the
+    one-engine pair: the flow records concatenated, the samples concatenated
+    with each rank's `flow` offset by the records of the ranks before it (a
+    rank's samples index its own flow array).  The result is sorted by (flow,
+    t) because each rank's is and the ranks' hosts are consecutive."""
+    flows, series, at = [], [], 0
+    for f, s in pairs:
+        f = np.asarray(f, dtype=TCP_FLOW_DTYPE)
+        s = np.asarray(s, dtype=TCP_SAMPLE_DTYPE).copy()
+        s["flow"] += at
+        at += len(f)
+        flows.append(f)
+        series.append(s)
+    if not flows:
+        return np.zeros(0, dtype=TCP_FLOW_DTYPE), np.zeros(0, dtype=TCP_SAMPLE_DTYPE)
+    return np.concatenate(flows), np.concatenate(series)
+
+
+def flow_progress(series, flows, interval_ns, end_ns) -> np.ndarray:
+    """The dense [n_flows, K + 1] cumulative bytes_delivered of every flow
+    record: column k (k < K) is the value at boundary T_(k+1) = (k + 1) *
+    interval_ns for the K boundaries before end_ns, the sparse samples filled
+    forward (0 before a record's first sample); the last column is the flow
+    record's own final value."""
+    flows = np.asarray(flows, dtype=TCP_FLOW_DTYPE)
+    s = np.asarray(series, dtype=TCP_SAMPLE_DTYPE)
+    interval_ns, end_ns = int(interval_ns), int(end_ns)
+    K = max((end_ns - 1) // interval_ns, 0)   # boundaries k * I < end, k >= 1
+    out = np.zeros((len(flows), K + 1), dtype=np.uint64)
+    if len(s):
+        k = (s["t"] // np.uint64(interval_ns)).astype(np.int64) - 1
+        assert ((s["t"] % np.uint64(interval_ns)) == 0).all() and (k >= 0).all() and (k < K).all()
+        out[s["flow"], k] = s["bytes_delivered"]
+    if K:
+        np.maximum.accumulate(out[:, :K], axis=1, out=out[:, :K])   # cumulative counters: forward fill
+    out[:, K] = flows["bytes_delivered"]
+    return out
 
 
 def ip_str(ip: int) -> str:

@@ -100,7 +100,8 @@ def serial_first_queries(queries: np.ndarray):
 
 def run(model: S.ModelArrays, g: S.GraphArrays, ips, procs, peers, nbytes=20000, trace=True,
         recv_buf=RECV_BUF, send_buf=SEND_BUF, tcp_window=TCP_WINDOW, packets_per_host=0, guess_reversed=False,
-        node=False, qdisc=0, mode="device", udp=None, comm=None, pcap=None, flows=False, paths=False):
+        node=False, qdisc=0, mode="device", udp=None, comm=None, pcap=None, flows=False, paths=False,
+        series_us=0, series_cap=0):
     """Run the TCP echo model on the GPU: procs = [(host, start ns)], peers =
     [-1 | server process]; ips: host-order uint32 per host.  Returns
     dict(lines=[(t, h, line)] in each host's order, next_event_id,
@@ -142,10 +143,21 @@ def run(model: S.ModelArrays, g: S.GraphArrays, ips, procs, peers, nbytes=20000,
     the table's indices are mapped back), so the two modes' arrays are equal
     byte for byte.  With comm the array is this rank's own hosts' sends;
     S.merge_tcp_paths sums the ranks'; S.write_paths_csv writes them.
+    series_us: the flow time series (shd_tcp_model.options &
+    SHD_TCP_OPT_SERIES) at that interval in microseconds; implies flows.  The
+    result then has series, a S.TCP_SAMPLE_DTYPE array sorted by (flow, t) --
+    one sample of a flow record's counters for every interval in which the
+    record changed, labelled with the interval's end, `flow` indexing the
+    result's flows -- and series_info dict(drains, peak, capacity);
+    series_cap: records of the device's sample array (0: the default).  With
+    comm the samples are this rank's own hosts'; S.merge_tcp_series joins the
+    ranks', S.flow_progress makes the dense curves, S.write_series_csv writes
+    the samples.
     The model's bootstrap period (model.struct.bootstrap_end) and per-host
     heartbeat intervals (model.host_heartbeat) run as the reference's loop runs
     them (shd_tcp_model.bootstrap_end / host_heartbeat), on one engine and
     with comm."""
+    flows = flows or bool(series_us)
     if mode == "device" and not guess_reversed and not g.directed:
         m = model.struct
         H = int(m.n_hosts)
@@ -156,7 +168,7 @@ def run(model: S.ModelArrays, g: S.GraphArrays, ips, procs, peers, nbytes=20000,
         try:
             out = _run_once(model, ips, procs, peers, None, None, hv.astype(np.int32), nbytes, trace, recv_buf,
                             send_buf, tcp_window, packets_per_host, node, qdisc, pc=pc, udp=udp, comm=comm,
-                            pcap=pcap, flows=flows, paths=paths)
+                            pcap=pcap, flows=flows, paths=paths, series_us=series_us, series_cap=series_cap)
         finally:
             pc.close()
         if out is not None:
@@ -168,7 +180,8 @@ def run(model: S.ModelArrays, g: S.GraphArrays, ips, procs, peers, nbytes=20000,
     V = lat.shape[0]
     for runs in range(1, 9):
         out = _run_once(model, ips, procs, peers, lat, rel, hvi, nbytes, trace, recv_buf, send_buf, tcp_window,
-                        packets_per_host, node, qdisc, udp=udp, comm=comm, pcap=pcap, flows=flows, paths=paths)
+                        packets_per_host, node, qdisc, udp=udp, comm=comm, pcap=pcap, flows=flows, paths=paths,
+                        series_us=series_us, series_cap=series_cap)
         if paths:   # the table's indices back to graph vertices
             p = out["paths"]
             names = np.asarray(att, dtype=np.int32)
@@ -194,13 +207,15 @@ def run(model: S.ModelArrays, g: S.GraphArrays, ips, procs, peers, nbytes=20000,
 
 def fill_model(model, ips, procs, peers, lat, rel, hvi, nbytes, recv_buf=RECV_BUF, send_buf=SEND_BUF,
                tcp_window=TCP_WINDOW, packets_per_host=0, qdisc=0, pc=None, udp=None, pcap=None, flows=False,
-               paths=False):
+               paths=False, series_us=0, series_cap=0):
     """The shd_tcp_model of one run (no device needed): (TcpModel, the arrays
     its pointers refer to -- keep them alive as long as the struct is used).
     The model's bootstrap period and per-host heartbeat intervals
     (model.struct.bootstrap_end, model.host_heartbeat: <shadow bootstraptime>,
     <host heartbeatfrequency>) go in as they are.  flows: SHD_TCP_OPT_FLOWS in
-    the model's options; paths: SHD_TCP_OPT_PATHS."""
+    the model's options; paths: SHD_TCP_OPT_PATHS; series_us: SHD_TCP_OPT_SERIES
+    at that interval (the caller sets flows with it: the library refuses the
+    bit alone), series_cap: the sample array's records (0: the default)."""
     m = model.struct
     H = int(m.n_hosts)
     keep = dict(ip=np.ascontiguousarray(ips, dtype=np.uint32), hv=np.ascontiguousarray(hvi, dtype=np.int32),
@@ -235,7 +250,10 @@ def fill_model(model, ips, procs, peers, lat, rel, hvi, nbytes, recv_buf=RECV_BU
     tm.tcp_window = tcp_window
     tm.packets_per_host = packets_per_host
     tm.qdisc = int(qdisc)   # --interface-qdisc: 0 fifo, 1 rr
-    tm.options = (S.TCP_OPT_FLOWS if flows else 0) | (S.TCP_OPT_PATHS if paths else 0)
+    tm.options = (S.TCP_OPT_FLOWS if flows else 0) | (S.TCP_OPT_PATHS if paths else 0) | \
+        (S.TCP_OPT_SERIES if series_us else 0)
+    tm.series_interval_us = int(series_us)
+    tm.series_cap = int(series_cap)
     if pc is not None:
         tm.path_cache = pc.ptr.value
     if udp is not None:
@@ -260,12 +278,13 @@ def fill_model(model, ips, procs, peers, lat, rel, hvi, nbytes, recv_buf=RECV_BU
 
 def _run_once(model, ips, procs, peers, lat, rel, hvi, nbytes, trace, recv_buf, send_buf, tcp_window,
               packets_per_host, node=False, qdisc=0, pc=None, udp=None, comm=None, pcap=None, flows=False,
-              paths=False):
+              paths=False, series_us=0, series_cap=0):
     """one shd_tcp_run on the given path tables, or with pc (sim.PathCache) on
     the cache itself (hvi: graph vertices then); None when that run's
     first-touch choices were contradicted (SHD_TCP_ERR_FIRST_TOUCH)"""
     tm, keep = fill_model(model, ips, procs, peers, lat, rel, hvi, nbytes, recv_buf, send_buf, tcp_window,
-                          packets_per_host, qdisc, pc=pc, udp=udp, pcap=pcap, flows=flows, paths=paths)
+                          packets_per_host, qdisc, pc=pc, udp=udp, pcap=pcap, flows=flows, paths=paths,
+                          series_us=series_us, series_cap=series_cap)
     res = C.POINTER(S.TcpResult)()
     bits = (S.TCP_TRACE_STATUS if trace else 0) | (S.TCP_TRACE_NODE if node else 0)
     if comm is not None:
@@ -300,6 +319,8 @@ def _run_once(model, ips, procs, peers, lat, rel, hvi, nbytes, trace, recv_buf, 
                    np.zeros(0, dtype=S.TCP_QUERY_DTYPE))
         if flows:
             out["flows"] = S.tcp_result_flows(res)
+        if series_us:
+            out["series"], out["series_info"] = S.tcp_result_series(res)
         if paths:
             out["paths"] = S.tcp_result_paths(res)
         if pcap is not None:
