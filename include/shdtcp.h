@@ -40,6 +40,18 @@
  * path_cache the sends also go into the cache's packet counter
  * (shd_pc_packet_count: the reference's Path.packetCount).
  *
+ * What a run says about where its packets waited without tracing: with
+ * SHD_TCP_OPT_HOSTS in shd_tcp_model.options, one host record
+ * (shd_tcp_hostrec) for every host -- what its upstream router queue (CoDel,
+ * the one place the reference models congestion) took in, handed on and
+ * dropped, how deep it got and how long the packets sat in it (sum, maximum
+ * and a 16-bucket histogram of the sojourn), what the interface received,
+ * dropped and sent, and how often a socket throttled a segment or took one
+ * out of order -- counted by the host's own lane where the reference raises
+ * the status, TCP packets and the datagrams of a mixed model alike, and copied
+ * to the host at the end (shd_tcp_result_hosts; tests/test_tcp_hosts_gpu.py
+ * against tests/golden/ref_tcp_hosts.json).
+ *
  * A host's shape comes from the model.  Its socket slots are the sockets it
  * can ever create -- a socket is not released in a TCP run: for each of its
  * server processes the listener and one child per client process that names
@@ -396,10 +408,46 @@ typedef struct shd_tcp_path {
                                       pair, either outcome; a record exists only for a pair that saw one */
 } shd_tcp_path;
 
+/* One host of a run with SHD_TCP_OPT_HOSTS: what its upstream router queue,
+ * its interface and its sockets' two TCP queues did, each field counted by
+ * the host's own lane where the reference raises the named status on that
+ * host, so every count is a number of [STATUS] lines of a traced run that the
+ * host executed (tests/tcp_host_expect.py).  Bytes are the packet's payload
+ * (the line's bytes=).  TCP packets and the datagrams of a mixed model count
+ * alike: the router and the interface serve both.  The router queue is FIFO
+ * and never refuses a packet (CODEL_PARAM_QUEUE_SIZE_LIMIT is G_MAXUINT), so
+ * every drop is a CoDel drop of the queue's head.  A host that saw no packet
+ * has a record that is zero apart from `host`.  Times are ns. */
+typedef struct shd_tcp_hostrec {
+    int32_t  host;                  /* the model's host index */
+    uint32_t depth_max;             /* the most packets the queue held right after a ROUTER_ENQUEUED, that packet included */
+    uint32_t depth_end;             /* packets still queued when the run ended: enqueued - dequeued - dropped */
+    uint32_t _pad;
+    uint64_t router_enqueued, router_enqueued_bytes;   /* ROUTER_ENQUEUED (router.c:113) */
+    uint64_t router_dequeued, router_dequeued_bytes;   /* ROUTER_DEQUEUED (router.c:129) */
+    uint64_t router_dropped, router_dropped_bytes;     /* ROUTER_DROPPED (router_queue_codel.c:139) */
+    uint64_t t_depth_max;           /* the first enqueue that reached depth_max */
+    /* over the dequeued packets only: a packet's sojourn is its ROUTER_DEQUEUED
+     * time minus its ROUTER_ENQUEUED time; t_sojourn_max is the first dequeue
+     * that reached the maximum */
+    uint64_t sojourn_sum, sojourn_max, t_sojourn_max;
+    uint64_t if_received, if_received_bytes;   /* RCV_INTERFACE_RECEIVED (network_interface.c:382), the
+                                                  loopback task's delivery included */
+    uint64_t if_dropped;                       /* RCV_INTERFACE_DROPPED (:411) */
+    uint64_t if_sent, if_sent_bytes;           /* SND_INTERFACE_SENT (:545), packets to the host's own address included */
+    uint64_t tcp_throttled;         /* SND_TCP_ENQUEUE_THROTTLED (tcp.c:743) */
+    uint64_t tcp_unordered;         /* RCV_TCP_ENQUEUE_UNORDERED (tcp.c:758) */
+    uint64_t t_first, t_last;       /* first and last time one of the statuses above was raised on the host; 0: never */
+    /* the dequeued packets by sojourn: bucket min(15, bit_length(sojourn >> 16)),
+     * bit_length(0) = 0 -- bucket 0 below 65.536 us, bucket k [2^(15+k), 2^(16+k))
+     * ns, bucket 15 2^30 ns (1.07 s) and above; they sum to router_dequeued */
+    uint32_t sojourn_hist[16];
+} shd_tcp_hostrec;
+
 /* shd_tcp_model.options: independent bits, but SHD_TCP_OPT_SERIES is valid only
  * together with SHD_TCP_OPT_FLOWS and a nonzero series_interval_us (-22
  * otherwise, before any device call) */
-enum { SHD_TCP_OPT_FLOWS = 1, SHD_TCP_OPT_PATHS = 2, SHD_TCP_OPT_SERIES = 4 };
+enum { SHD_TCP_OPT_FLOWS = 1, SHD_TCP_OPT_PATHS = 2, SHD_TCP_OPT_SERIES = 4, SHD_TCP_OPT_HOSTS = 8 };
 
 /* The most entries the device's pair table gets (SHD_TCP_OPT_PATHS; 64 bytes
  * each: 256 MiB).  Its capacity is a power of two at least twice min(Vu^2, E +
@@ -493,6 +541,20 @@ int shd_tcp_result_paths(const shd_tcp_result* r, const shd_tcp_path** recs, uin
  * start (first_touch_reruns) starts the series again with the records. */
 int shd_tcp_result_series(const shd_tcp_result* r, const shd_tcp_sample** recs, uint64_t* n,
                           shd_tcp_series_info* info);
+
+/* The host records of the hosts this result covers (a result of shd_tcp_run /
+ * shd_tcp_run_group only): a dense array, *n == n_local_hosts, record i
+ * describing host first_host + i, so a group's ranks concatenated in rank
+ * order are the one-engine array -- nothing is exchanged between ranks.
+ * *recs NULL and *n 0 when the model did not set SHD_TCP_OPT_HOSTS.  Owned by
+ * the result.  Returns 0, -22 for a NULL argument.  The records have a fixed
+ * size, so nothing can overflow and the option has no error bit.  Without the
+ * option a run allocates nothing for them, launches nothing extra and runs
+ * the rounds as before; a rerun from the start (first_touch_reruns) starts the
+ * records again.  SHD_TCP_HOST_TIMING in the environment (any value) makes a
+ * run with the option print, on stderr, the size and the host wall time of
+ * the records' copy at its end (measurements: profiles/hosts/ab.txt). */
+int shd_tcp_result_hosts(const shd_tcp_result* r, const shd_tcp_hostrec** recs, uint64_t* n);
 
 /* The same model on a group of engines, one per process and GPU (shdgpu.h
  * shd_comm: RCCL, or the host-memory transport for several processes on one

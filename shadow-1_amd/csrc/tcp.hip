@@ -42,6 +42,9 @@
 // lane crosses an interval boundary (series_cross, series_take) into one
 // engine-wide array that the host empties between batches of rounds
 // (series_drain), and what is still touched at the end by k_tcp_series_flush.
+// With SHD_TCP_OPT_HOSTS each host's lane counts what its router queue, its
+// interface and its sockets' throttled and unordered queues did into the
+// host's shd_tcp_hostrec (host_status), copied to the host at the end.
 //
 // The work is branchy per-host control flow with a few events per host and
 // round: latency-bound by design ("TCP"); it shares nothing with
@@ -304,6 +307,7 @@ struct DFlow {
 };
 static_assert(sizeof(DFlow) == 104, "a flow record beside each socket slot");
 constexpr uint32_t kFlowTouched = 1u << 31;
+static_assert(sizeof(shd_tcp_hostrec) == 232, "a host record, kept on the device in its public form");
 // A socket slot's path accumulator (shd_tcp_model.options & SHD_TCP_OPT_PATHS):
 // Glob::pacc, one per slot beside the socket, not in it: what the slot's
 // packets added to the record of its current vertex pair (va, vb: Glob::hv's
@@ -469,6 +473,10 @@ struct Glob {
     uint32_t* nser;
     uint64_t* ser_next;
     uint64_t ser_ival;
+    // host records (SHD_TCP_OPT_HOSTS): hrec [nloc], each local host's record in
+    // its public form, written by the host's own lane only with plain stores;
+    // null without the option.  stat_on's fourth bit (8) says they are kept.
+    shd_tcp_hostrec* hrec;
 };
 struct XSegHead { uint32_t n, nsack, err, _pad[13]; };   // 64 B, then xcap Mails, then xsack_cap SACK words
 static_assert(sizeof(XSegHead) == 64, "segment header");
@@ -712,13 +720,20 @@ __device__ bool sched_task(L& c, uint64_t delay, uint32_t kind, int32_t obj) {
 // and at worker_send_packet's two (path_status)
 __device__ void flow_status(L& c, const DSock* k, const DPkt* p, uint8_t st);
 __device__ __forceinline__ void path_status(L& c, const DSock* k, const DPkt* p, uint8_t st);
+// the statuses a host record counts (host_status)
+__device__ __forceinline__ void host_status(L& c, const DPkt* p, uint32_t st);
+__device__ __forceinline__ constexpr bool host_counts(uint8_t st) {
+    return st == S_ROUTER_ENQUEUED || st == S_ROUTER_DEQUEUED || st == S_ROUTER_DROPPED ||
+           st == S_RCV_INTERFACE_RECEIVED || st == S_RCV_INTERFACE_DROPPED || st == S_SND_INTERFACE_SENT ||
+           st == S_SND_TCP_ENQUEUE_THROTTLED || st == S_RCV_TCP_ENQUEUE_UNORDERED;
+}
 __device__ void pkt_status(L& c, int32_t pi, uint8_t st, uint32_t trflags = 0,
                            const DSock* k = nullptr) {   // packet_addDeliveryStatus (packet.c:647-659)
     DPkt* p = PK(c, pi);
     DHost* H = c.H;
     if (st == S_SND_TCP_RETRANSMITTED) p->xflags |= kXRetx;   // packet_getDeliveryStatus's OR of every status
     // one word says what a status feeds besides the packet: the lines (1),
-    // the flow records (2) and the path records (4).  A run with none leaves
+    // the flow records (2), the path records (4) and the host records (8).  A run with none leaves
     // here as it did when the word was Glob::trace alone: the records cost it
     // no test of their own.
     const uint32_t on = c.g->stat_on;
@@ -727,6 +742,10 @@ __device__ void pkt_status(L& c, int32_t pi, uint8_t st, uint32_t trflags = 0,
     // (st is a constant where pkt_status is inlined: the count exists at worker_send_packet's two sites only,
     // and every other function keeps the code it had)
     if ((st == S_INET_SENT || st == S_INET_DROPPED) && (on & 4u)) path_status(c, k, p, st);
+    // (likewise: the count exists at the eight sites that raise a counted status, behind a branch marked
+    // unlikely.  Inlined: out of line, as a call, the same code cost the run WITHOUT the option 0.25 %, and
+    // as one specialised function per status 1.4 % -- profiles/hosts/ab.txt)
+    if (host_counts(st) && __builtin_expect((on & 8u) != 0, 0)) host_status(c, p, st);
     if (!(on & 1u)) return;   // the list is read by the lines only
     if (p->nst < kSt) p->st[p->nst++] = st;
     else H->err |= SHD_TCP_ERR_TRACE;   // a line would lose statuses: fail, never truncate
@@ -940,6 +959,63 @@ __device__ __forceinline__ void path_status(L& c, const DSock* k, const DPkt* p,
     } else {
         a->packets_dropped++;
         a->bytes_dropped += p->len;
+    }
+}
+
+// ------------------------------------------------------------ host records (shd_tcp_hostrec)
+// The count points: the eight statuses of the router queue (router.c:113, 129,
+// router_queue_codel.c:139), the interface (network_interface.c:382, 411, 545)
+// and the two TCP queues (tcp.c:743, 758), each raised on the packet by the
+// executing host, whose record takes it: the lane is its record's only writer
+// (plain loads and stores).  The depth is DHost::cq_n right after the enqueue
+// (K_DELIVER raises the status after the entry is in), the sojourn the event's
+// time minus the entry's enqueue time: ROUTER_DEQUEUED is raised on the entry
+// cq_helper popped last, which still lies in the ring right before the head.
+__device__ __forceinline__ void host_status(L& c, const DPkt* p, uint32_t st) {
+    shd_tcp_hostrec* r = &c.g->hrec[c.h];
+    const uint64_t now = c.now, len = p->len;
+    if (!r->t_first) r->t_first = now;
+    r->t_last = now;
+    switch (st) {
+    case S_ROUTER_ENQUEUED: {
+        r->router_enqueued++;
+        r->router_enqueued_bytes += len;
+        const uint32_t d = c.H->cq_n;
+        if (d > r->depth_max) { r->depth_max = d; r->t_depth_max = now; }
+        break;
+    }
+    case S_ROUTER_DEQUEUED: {
+        r->router_dequeued++;
+        r->router_dequeued_bytes += len;
+        const uint64_t so = now - c.g->cq[(size_t)c.h * kCq + (c.H->cq_head + kCq - 1) % kCq].ts;
+        r->sojourn_sum += so;
+        if (so > r->sojourn_max || r->router_dequeued == 1) { r->sojourn_max = so; r->t_sojourn_max = now; }
+        const uint64_t hi = so >> 16;   // bucket min(15, bit_length(sojourn >> 16))
+        const uint32_t b = hi ? 64u - (uint32_t)__clzll((long long)hi) : 0u;
+        r->sojourn_hist[b < 15u ? b : 15u]++;
+        break;
+    }
+    case S_ROUTER_DROPPED:
+        r->router_dropped++;
+        r->router_dropped_bytes += len;
+        break;
+    case S_RCV_INTERFACE_RECEIVED:
+        r->if_received++;
+        r->if_received_bytes += len;
+        break;
+    case S_RCV_INTERFACE_DROPPED:
+        r->if_dropped++;
+        break;
+    case S_SND_INTERFACE_SENT:
+        r->if_sent++;
+        r->if_sent_bytes += len;
+        break;
+    case S_SND_TCP_ENQUEUE_THROTTLED:
+        r->tcp_throttled++;
+        break;
+    default:   // S_RCV_TCP_ENQUEUE_UNORDERED
+        r->tcp_unordered++;
+        break;
     }
 }
 
@@ -3678,7 +3754,7 @@ enum WsSlot {
     kWsAppSpec, kWsAppPeer, kWsDestCum, kWsHostClass, kWsIpAll, kWsBwu, kWsBwd, kWsProcPort, kWsPortNew, kWsXsend,
     kWsXrecv, kWsPmine, kWsPall, kWsXcnt, kWsGmine, kWsGall, kWsPcap, kWsNpcap, kWsPcapSlot, kWsHostHb, kWsSockOff, kWsDir, kWsIfq,
     kWsProcOff, kWsFlow, kWsFlowCnt, kWsFlowOff, kWsFlowOut, kWsPacc, kWsPtab, kWsPtFull, kWsPtCnt, kWsPtOff,
-    kWsPtOut, kWsSer, kWsNser, kWsSerNext, kWsSerMap, kWsSlots
+    kWsPtOut, kWsSer, kWsNser, kWsSerNext, kWsSerMap, kWsHrec, kWsSlots
 };
 // what the library allocates for a result: the public struct first (its size
 // is pinned), then the flow records shd_tcp_result_flows and the path records
@@ -3692,6 +3768,8 @@ struct TcpResultX {
     shd_tcp_sample* series;   // shd_tcp_result_series: sorted by (flow, t)
     uint64_t n_series;
     shd_tcp_series_info series_info;
+    shd_tcp_hostrec* hosts;   // shd_tcp_result_hosts: n_local_hosts records, or null without the option
+    uint64_t n_hosts;
 };
 // The pair table's capacity (shdtcp.h): a power of two at least twice the
 // most ordered vertex pairs the model's hosts can send over -- min(Vu^2, E + 2
@@ -4305,6 +4383,16 @@ static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, s
             g.path_on = 1;
             g.stat_on |= 4u;
         }
+        if (m->options & SHD_TCP_OPT_HOSTS) {   // a record per local host, zero at the start of every run (a rerun's too)
+            if (ws_alloc(ws, kWsHrec, &g.hrec, sizeof(shd_tcp_hostrec) * (size_t)nloc) != hipSuccess) {
+                (void)hipGetLastError();
+                fprintf(stderr, "shd_tcp_run: no device memory for the host records of %d hosts\n", nloc);
+                rc = -12;
+                goto done;
+            }
+            HCHECK(hipMemset(g.hrec, 0, sizeof(shd_tcp_hostrec) * (size_t)nloc));
+            g.stat_on |= 8u;
+        }
         HCHECK(ws_alloc(ws, kWsProcOff, &d_hpo, sizeof(int32_t) * hpo.size()));
         HCHECK(hipMemcpy(d_hpo, hpo.data(), sizeof(int32_t) * hpo.size(), hipMemcpyHostToDevice));
         g.proc_off = d_hpo;
@@ -4806,6 +4894,20 @@ static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, s
         res->error |= hout[i].err;
         res->max_host_sockets = std::max<uint32_t>(res->max_host_sockets, (uint32_t)hout[i].nsock);
     }
+    if (g.hrec) {   // the local hosts' records in one copy; the host names them and reads the queue's last length
+        const auto t0 = std::chrono::steady_clock::now();
+        resx->hosts = (shd_tcp_hostrec*)malloc(sizeof(shd_tcp_hostrec) * (size_t)(nloc ? nloc : 1));
+        if (!resx->hosts) { rc = -12; goto done; }
+        HCHECK(hipMemcpy(resx->hosts, g.hrec, sizeof(shd_tcp_hostrec) * (size_t)nloc, hipMemcpyDeviceToHost));
+        for (int32_t i = 0; i < nloc; i++) {
+            resx->hosts[i].host = h0 + i;
+            resx->hosts[i].depth_end = hout[i].cq_n;
+        }
+        resx->n_hosts = (uint64_t)nloc;
+        if (getenv("SHD_TCP_HOST_TIMING"))   // the copy's size and host wall time, for measurements
+            fprintf(stderr, "shd_tcp_run: %d host records (%zu bytes) copied in %.3f ms\n", nloc,
+                    sizeof(shd_tcp_hostrec) * (size_t)nloc, ms_since(t0));
+    }
     if (g.path_on && pc && !res->error) {
         // Path.packetCount (topology_incrementPathPacketCounter, worker.c:296):
         // the cache's own counter, keyed on the unordered attached pair as
@@ -4925,7 +5027,16 @@ extern "C" void shd_tcp_result_free(shd_tcp_result* r) {
     free(((TcpResultX*)r)->flows);   // (every result is allocated as a TcpResultX: tcp_run_impl)
     free(((TcpResultX*)r)->paths);
     free(((TcpResultX*)r)->series);
+    free(((TcpResultX*)r)->hosts);
     free(r);
+}
+
+extern "C" int shd_tcp_result_hosts(const shd_tcp_result* r, const shd_tcp_hostrec** recs, uint64_t* n) {
+    if (!r || !recs || !n) return -22;
+    const TcpResultX* x = (const TcpResultX*)r;
+    *recs = x->n_hosts ? x->hosts : nullptr;
+    *n = x->n_hosts;
+    return 0;
 }
 
 extern "C" int shd_tcp_result_series(const shd_tcp_result* r, const shd_tcp_sample** recs, uint64_t* n,

@@ -313,6 +313,28 @@ TCP_SAMPLE_DTYPE = np.dtype([("t", "<u8"), ("flow", "<u4"), ("host", "<i4"),
 assert TCP_SAMPLE_DTYPE.itemsize == C.sizeof(TcpSample) == 96
 
 
+class TcpHostRec(C.Structure):
+    """shd_tcp_hostrec (include/shdtcp.h): one host's router queue, interface and TCP queue counts"""
+    _fields_ = [("host", C.c_int32), ("depth_max", C.c_uint32), ("depth_end", C.c_uint32), ("_pad", C.c_uint32),
+                ("router_enqueued", C.c_uint64), ("router_enqueued_bytes", C.c_uint64),
+                ("router_dequeued", C.c_uint64), ("router_dequeued_bytes", C.c_uint64),
+                ("router_dropped", C.c_uint64), ("router_dropped_bytes", C.c_uint64),
+                ("t_depth_max", C.c_uint64),
+                ("sojourn_sum", C.c_uint64), ("sojourn_max", C.c_uint64), ("t_sojourn_max", C.c_uint64),
+                ("if_received", C.c_uint64), ("if_received_bytes", C.c_uint64), ("if_dropped", C.c_uint64),
+                ("if_sent", C.c_uint64), ("if_sent_bytes", C.c_uint64),
+                ("tcp_throttled", C.c_uint64), ("tcp_unordered", C.c_uint64),
+                ("t_first", C.c_uint64), ("t_last", C.c_uint64),
+                ("sojourn_hist", C.c_uint32 * 16)]
+
+
+TCP_OPT_HOSTS = 8   # SHD_TCP_OPT_HOSTS (shd_tcp_model.options): a record per host of its router queue and interface
+# shd_tcp_hostrec as a structured dtype (the records shd_tcp_result_hosts hands out); times in ns
+TCP_HOSTREC_DTYPE = np.dtype([(n, "<i4" if t is C.c_int32 else "<u4" if t is C.c_uint32 else "<u8")
+                              if n != "sojourn_hist" else (n, "<u4", (16,)) for n, t in TcpHostRec._fields_])
+assert TCP_HOSTREC_DTYPE.itemsize == C.sizeof(TcpHostRec) == 232
+
+
 TCP_QUERY_DTYPE = np.dtype([("time", "<u8"), ("seq", "<u8"), ("host", "<u4"), ("src", "<u4"), ("index", "<u4"),
                             ("v_src", "<i4"), ("v_dst", "<i4"), ("_pad", "<u4")])   # shd_tcp_query
 
@@ -331,6 +353,7 @@ _SIGS = {
     "shd_tcp_result_flows": (C.c_int, [P(TcpResult), P(P(TcpFlow)), P(C.c_uint64)]),
     "shd_tcp_result_paths": (C.c_int, [P(TcpResult), P(P(TcpPath)), P(C.c_uint64)]),
     "shd_tcp_result_series": (C.c_int, [P(TcpResult), P(P(TcpSample)), P(C.c_uint64), P(TcpSeriesInfo)]),
+    "shd_tcp_result_hosts": (C.c_int, [P(TcpResult), P(P(TcpHostRec)), P(C.c_uint64)]),
     "shd_tcp_keep_workspace": (None, [C.c_int32]),
     "shd_pcap_format": (C.c_size_t, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int32, C.c_void_p, C.c_size_t]),
     "shd_pcap_write_host": (C.c_int, [C.c_char_p, C.c_char_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32]),
@@ -629,6 +652,49 @@ def write_paths_csv(path, recs) -> int:
         for r in a:
             out.write(",".join(str(int(r[k])) for k in TCP_PATH_DTYPE.names) + "\n")
     return len(a)
+
+
+def tcp_result_hosts(res) -> np.ndarray:
+    """The host records of a shd_tcp_result (pointer) as a TCP_HOSTREC_DTYPE
+    array of its own (shd_tcp_result_hosts), one per host the result covers in
+    host order; empty when the model did not set TCP_OPT_HOSTS."""
+    recs, n = P(TcpHostRec)(), C.c_uint64()
+    check(lib().shd_tcp_result_hosts(res, C.byref(recs), C.byref(n)), "shd_tcp_result_hosts")
+    if not n.value:
+        return np.zeros(0, dtype=TCP_HOSTREC_DTYPE)
+    return np.frombuffer(C.string_at(recs, n.value * TCP_HOSTREC_DTYPE.itemsize), dtype=TCP_HOSTREC_DTYPE).copy()
+
+
+HOSTS_HIST_BUCKETS = 16
+# the columns of write_hosts_csv: the record's fields without the padding, the histogram as 16 columns
+HOSTS_CSV_FIELDS = tuple(k for k in TCP_HOSTREC_DTYPE.names if k not in ("_pad", "sojourn_hist")) + \
+    tuple("sojourn_hist_%d" % i for i in range(HOSTS_HIST_BUCKETS))
+
+
+def write_hosts_csv(path, recs) -> int:
+    """Write host records (TCP_HOSTREC_DTYPE, as tcp.run(..., hosts=True)
+    returns them) as CSV: a header line (HOSTS_CSV_FIELDS), then one line per
+    host in the records' order; times and sojourns in ns, bucket k of the
+    histogram in column sojourn_hist_k.  Returns the number of rows."""
+    a = np.asarray(recs, dtype=TCP_HOSTREC_DTYPE)
+    scalars = HOSTS_CSV_FIELDS[:-HOSTS_HIST_BUCKETS]
+    with open(path, "w") as out:
+        out.write(",".join(HOSTS_CSV_FIELDS) + "\n")
+        for r in a:
+            out.write(",".join([str(int(r[k])) for k in scalars] + [str(int(v)) for v in r["sojourn_hist"]]) + "\n")
+    return len(a)
+
+
+def merge_tcp_hosts(parts) -> np.ndarray:
+    """The host records of a group's ranks (TCP_HOSTREC_DTYPE arrays) in rank
+    order as the one-engine array: each rank holds its own hosts' records and
+    the ranks' hosts are consecutive, so they are concatenated; the `host`
+    values must then be 0 .. H-1 (ValueError otherwise)."""
+    parts = [np.asarray(a, dtype=TCP_HOSTREC_DTYPE) for a in parts]
+    out = np.concatenate(parts) if parts else np.zeros(0, dtype=TCP_HOSTREC_DTYPE)
+    if out["host"].tolist() != list(range(len(out))):
+        raise ValueError("merge_tcp_hosts: the ranks' records do not cover hosts 0 .. H-1 in order")
+    return out
 
 
 def tcp_result_series(res):

@@ -101,7 +101,7 @@ def serial_first_queries(queries: np.ndarray):
 def run(model: S.ModelArrays, g: S.GraphArrays, ips, procs, peers, nbytes=20000, trace=True,
         recv_buf=RECV_BUF, send_buf=SEND_BUF, tcp_window=TCP_WINDOW, packets_per_host=0, guess_reversed=False,
         node=False, qdisc=0, mode="device", udp=None, comm=None, pcap=None, flows=False, paths=False,
-        series_us=0, series_cap=0):
+        series_us=0, series_cap=0, hosts=False):
     """Run the TCP echo model on the GPU: procs = [(host, start ns)], peers =
     [-1 | server process]; ips: host-order uint32 per host.  Returns
     dict(lines=[(t, h, line)] in each host's order, next_event_id,
@@ -153,6 +153,13 @@ def run(model: S.ModelArrays, g: S.GraphArrays, ips, procs, peers, nbytes=20000,
     comm the samples are this rank's own hosts'; S.merge_tcp_series joins the
     ranks', S.flow_progress makes the dense curves, S.write_series_csv writes
     the samples.
+    hosts: a record for every host the result covers of what its upstream
+    router queue, its interface and its sockets' throttled and unordered queues
+    did (shd_tcp_model.options & SHD_TCP_OPT_HOSTS), with or without trace and
+    the other options: the result then has hosts, a S.TCP_HOSTREC_DTYPE array
+    in host order, record i for host first_host + i.  With comm the array is
+    this rank's own hosts'; S.merge_tcp_hosts joins the ranks',
+    S.write_hosts_csv writes them.
     The model's bootstrap period (model.struct.bootstrap_end) and per-host
     heartbeat intervals (model.host_heartbeat) run as the reference's loop runs
     them (shd_tcp_model.bootstrap_end / host_heartbeat), on one engine and
@@ -168,7 +175,8 @@ def run(model: S.ModelArrays, g: S.GraphArrays, ips, procs, peers, nbytes=20000,
         try:
             out = _run_once(model, ips, procs, peers, None, None, hv.astype(np.int32), nbytes, trace, recv_buf,
                             send_buf, tcp_window, packets_per_host, node, qdisc, pc=pc, udp=udp, comm=comm,
-                            pcap=pcap, flows=flows, paths=paths, series_us=series_us, series_cap=series_cap)
+                            pcap=pcap, flows=flows, paths=paths, series_us=series_us, series_cap=series_cap,
+                            hosts=hosts)
         finally:
             pc.close()
         if out is not None:
@@ -181,7 +189,7 @@ def run(model: S.ModelArrays, g: S.GraphArrays, ips, procs, peers, nbytes=20000,
     for runs in range(1, 9):
         out = _run_once(model, ips, procs, peers, lat, rel, hvi, nbytes, trace, recv_buf, send_buf, tcp_window,
                         packets_per_host, node, qdisc, udp=udp, comm=comm, pcap=pcap, flows=flows, paths=paths,
-                        series_us=series_us, series_cap=series_cap)
+                        series_us=series_us, series_cap=series_cap, hosts=hosts)
         if paths:   # the table's indices back to graph vertices
             p = out["paths"]
             names = np.asarray(att, dtype=np.int32)
@@ -207,7 +215,7 @@ def run(model: S.ModelArrays, g: S.GraphArrays, ips, procs, peers, nbytes=20000,
 
 def fill_model(model, ips, procs, peers, lat, rel, hvi, nbytes, recv_buf=RECV_BUF, send_buf=SEND_BUF,
                tcp_window=TCP_WINDOW, packets_per_host=0, qdisc=0, pc=None, udp=None, pcap=None, flows=False,
-               paths=False, series_us=0, series_cap=0):
+               paths=False, series_us=0, series_cap=0, hosts=False):
     """The shd_tcp_model of one run (no device needed): (TcpModel, the arrays
     its pointers refer to -- keep them alive as long as the struct is used).
     The model's bootstrap period and per-host heartbeat intervals
@@ -215,7 +223,8 @@ def fill_model(model, ips, procs, peers, lat, rel, hvi, nbytes, recv_buf=RECV_BU
     <host heartbeatfrequency>) go in as they are.  flows: SHD_TCP_OPT_FLOWS in
     the model's options; paths: SHD_TCP_OPT_PATHS; series_us: SHD_TCP_OPT_SERIES
     at that interval (the caller sets flows with it: the library refuses the
-    bit alone), series_cap: the sample array's records (0: the default)."""
+    bit alone), series_cap: the sample array's records (0: the default); hosts:
+    SHD_TCP_OPT_HOSTS."""
     m = model.struct
     H = int(m.n_hosts)
     keep = dict(ip=np.ascontiguousarray(ips, dtype=np.uint32), hv=np.ascontiguousarray(hvi, dtype=np.int32),
@@ -251,7 +260,7 @@ def fill_model(model, ips, procs, peers, lat, rel, hvi, nbytes, recv_buf=RECV_BU
     tm.packets_per_host = packets_per_host
     tm.qdisc = int(qdisc)   # --interface-qdisc: 0 fifo, 1 rr
     tm.options = (S.TCP_OPT_FLOWS if flows else 0) | (S.TCP_OPT_PATHS if paths else 0) | \
-        (S.TCP_OPT_SERIES if series_us else 0)
+        (S.TCP_OPT_SERIES if series_us else 0) | (S.TCP_OPT_HOSTS if hosts else 0)
     tm.series_interval_us = int(series_us)
     tm.series_cap = int(series_cap)
     if pc is not None:
@@ -278,13 +287,13 @@ def fill_model(model, ips, procs, peers, lat, rel, hvi, nbytes, recv_buf=RECV_BU
 
 def _run_once(model, ips, procs, peers, lat, rel, hvi, nbytes, trace, recv_buf, send_buf, tcp_window,
               packets_per_host, node=False, qdisc=0, pc=None, udp=None, comm=None, pcap=None, flows=False,
-              paths=False, series_us=0, series_cap=0):
+              paths=False, series_us=0, series_cap=0, hosts=False):
     """one shd_tcp_run on the given path tables, or with pc (sim.PathCache) on
     the cache itself (hvi: graph vertices then); None when that run's
     first-touch choices were contradicted (SHD_TCP_ERR_FIRST_TOUCH)"""
     tm, keep = fill_model(model, ips, procs, peers, lat, rel, hvi, nbytes, recv_buf, send_buf, tcp_window,
                           packets_per_host, qdisc, pc=pc, udp=udp, pcap=pcap, flows=flows, paths=paths,
-                          series_us=series_us, series_cap=series_cap)
+                          series_us=series_us, series_cap=series_cap, hosts=hosts)
     res = C.POINTER(S.TcpResult)()
     bits = (S.TCP_TRACE_STATUS if trace else 0) | (S.TCP_TRACE_NODE if node else 0)
     if comm is not None:
@@ -323,6 +332,8 @@ def _run_once(model, ips, procs, peers, lat, rel, hvi, nbytes, trace, recv_buf, 
             out["series"], out["series_info"] = S.tcp_result_series(res)
         if paths:
             out["paths"] = S.tcp_result_paths(res)
+        if hosts:
+            out["hosts"] = S.tcp_result_hosts(res)
         if pcap is not None:
             off = np.ctypeslib.as_array(r.pcap_off, shape=(HL + 1,)).copy()
             recs = np.frombuffer(C.string_at(r.pcap_records, int(off[-1]) * S.PCAP_DTYPE.itemsize),
