@@ -9,7 +9,8 @@ per process (profiles/hosts/ab.txt):
 
 One warm-up run, then `runs` timed ones (default 3) with the workspace kept, as
 the bench runs them.  Prints per run the events, rounds, device time of the
-rounds, M events/s and device time per round; SHD_TCP_HOST_TIMING=1 adds the
+rounds, M events/s, device time per round and the call's host times (setup,
+results, teardown: shd_tcp_result's); SHD_TCP_HOST_TIMING=1 adds the
 size and host wall time of the records' copy on stderr.  AB_HOSTS: another
 host count."""
 import os
@@ -46,9 +47,11 @@ def main():
             extra = " records=%d enqueued=%d dropped=%d depth_max=%d sojourn_max_ns=%d" % (
                 len(h), int(h["router_enqueued"].sum()), int(h["router_dropped"].sum()), int(h["depth_max"].max()),
                 int(h["sojourn_max"].max()))
-        print("%s run%d events=%d rounds=%d device_ms=%.3f Mev/s=%.3f us/round=%.3f results_ms=%.1f%s" % (
-            variant, i, r["events"], r["rounds"], r["device_ms"], r["events"] / r["device_ms"] / 1e3,
-            r["device_ms"] * 1e3 / r["rounds"], r["host_ms"]["results"], extra), flush=True)
+        print("%s run%d events=%d rounds=%d device_ms=%.3f Mev/s=%.3f us/round=%.3f setup_ms=%.1f results_ms=%.1f "
+              "teardown_ms=%.1f%s" % (
+                  variant, i, r["events"], r["rounds"], r["device_ms"], r["events"] / r["device_ms"] / 1e3,
+                  r["device_ms"] * 1e3 / r["rounds"], r["host_ms"]["setup"], r["host_ms"]["results"],
+                  r["host_ms"]["teardown"], extra), flush=True)
     S.lib().shd_tcp_keep_workspace(0)
 
 

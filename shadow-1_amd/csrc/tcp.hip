@@ -3466,7 +3466,7 @@ __global__ void __launch_bounds__(64) k_tcp_round(Glob g) {
 #endif
 }
 
-#define HCHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "shd_tcp: %s: %s\n", #x, hipGetErrorString(e_)); rc = -5; goto done; } } while (0)
+#define HCHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "shd_tcp: %s: %s\n", #x, hipGetErrorString(e_)); return -5; } } while (0)
 
 // The reference keeps a socket's retransmit queue in a GHashTable keyed by
 // sequence and clears it through an iterator (_tcp_clearRetransmit,
@@ -3857,9 +3857,6 @@ extern "C" void shd_tcp_keep_workspace(int32_t keep) {
     (void)hipSetDevice(cur);
 }
 
-// shd_tcp_run on one engine (comm null) or on this engine's share of a group
-// (shd_tcp_run_group: hosts [h0, h0 + nloc), the round's window agreed over
-// the group, deliveries between engines exchanged after every round)
 // one engine's first-touch schedule across the reruns of one shd_tcp_run call
 // (Glob::sched_*): a run whose round R contradicts a device choice that changes
 // a value stops there; the ranks that round's replay assigned, in serial order,
@@ -3988,80 +3985,57 @@ static bool tcp_host_slots(const shd_tcp_model* m, int32_t h0, int32_t nloc, std
     return true;
 }
 
-static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, shd_tcp_result** out,
-                        TcpSched* sch = nullptr) {
-    const auto t_call = std::chrono::steady_clock::now();
-    auto t_results = t_call;
-    shd_pc* pc = m ? m->path_cache : nullptr;
-    const int32_t world = comm ? comm->world : 1, me = comm ? comm->rank : 0;
-    if (!m || !out || m->n_hosts <= 0 || m->n_hosts > (1 << 26) || m->n_procs < 0 || !m->host_ip || !m->host_seed || !m->bw_down_kibps ||
-        !m->bw_up_kibps || (!pc && (!m->path_lat_ms || !m->path_rel || m->n_vertices <= 0)) || !m->host_vertex ||
-        (m->n_procs && (!m->proc_host || !m->proc_start || !m->proc_peer)))
-        return -22;
-    // the flow time series samples flow records at an interval: the bit needs both
-    if ((m->options & SHD_TCP_OPT_SERIES) &&
-        (!(m->options & SHD_TCP_OPT_FLOWS) || !m->series_interval_us || m->series_cap > (int32_t)kSeriesCapMax))
-        return -22;
-    // path_cache mode: a built cache of an undirected graph (the directed
-    // lookup reruns rows, topology.c:1987-1990: not restated on the device)
-    if (pc && (!pc->built || pc->directed || (!pc->complete && !pc->d_row))) return -22;
+// a phase's step that returns 0 or the run's code
+#define TRY(x) do { const int r_ = (x); if (r_) return r_; } while (0)
+
+static int32_t proc_app_of(const shd_tcp_model* m, int32_t k) { return m->proc_app ? m->proc_app[k] : -1; }
+
+// Phase 1, the plan: what the model alone decides about this engine's run of
+// hosts [h0, h0 + nloc) -- or the code the model is refused with.  Every
+// refusal is here, in a fixed order, before the run opens a device; only
+// path_cache mode's window reads the cache's device tables (tcp_pc_prep).
+struct TcpPlan {
+    int32_t world = 1, me = 0;
+    int32_t h0 = 0, nloc = 0;
+    int32_t V = 0;                      // the tables' vertices, or the cache's attached ones
+    std::vector<int32_t> hvi;           // each host's table index: the given one, or its attached index in the cache
+    std::vector<int32_t> per_vertex;    // hosts on each of them
+    bool any_udp = false, any_pcap = false;
+    uint32_t pool_cap = 0;
+    uint64_t W = ~0ull;                 // the rounds' window, ns
+    std::vector<int32_t> so, hpo, hp;   // this engine's hosts: their socket slots and processes as ranges (tcp_host_slots)
+    uint32_t max_procs = 0;
+    uint64_t hb_min = 0;                // the smallest heartbeat interval among this engine's hosts (node_k)
+    std::vector<uint64_t> ipk;          // host_of_ip's table, ip_mask + 1 entries
+    uint32_t ip_mask = 0;
+};
+
+// the datagram processes' applications (shd_tcp_model's comment)
+static int plan_datagram_apps(const shd_tcp_model* m) {
     const int32_t H = m->n_hosts, P = m->n_procs;
-    if (world > H || world > 64) return -22;   // (the group's per-engine tables below hold 64)
-    const int32_t h0 = (int32_t)(((int64_t)me * H) / world);
-    const int32_t nloc = (int32_t)(((int64_t)(me + 1) * H) / world) - h0;
-    auto app_of = [&](int32_t k) { return m->proc_app ? m->proc_app[k] : -1; };
-    bool any_udp = false;
+    if (!m->app_spec || m->n_app_specs <= 0 || m->udp_payload < 1 || m->udp_payload > kDgramMax) return -22;
+    std::vector<uint8_t> seen(H, 0);
     for (int32_t k = 0; k < P; k++) {
-        if (m->proc_host[k] < 0 || m->proc_host[k] >= H) return -22;
-        if (m->proc_peer[k] >= P || (m->proc_peer[k] >= 0 && m->proc_peer[m->proc_peer[k]] >= 0)) return -22;
-        // a client's server runs the echo; a datagram process has no echo peer
-        if (m->proc_peer[k] >= 0 && app_of(m->proc_peer[k]) >= 0) return -22;
-        if (app_of(k) >= 0 && m->proc_peer[k] >= 0) return -22;
-        any_udp |= app_of(k) >= 0;
+        const int32_t a = proc_app_of(m, k);
+        if (a < 0) continue;
+        if (a >= m->n_app_specs || seen[m->proc_host[k]]++) return -22;
+        const uint32_t* s = m->app_spec + 4 * (size_t)a;
+        if (s[0] > 2 || s[1] > 2 || s[3] > 1) return -22;
+        if (s[1] == 0 && !m->dest_cum) return -22;
+        if (s[1] == 1 && (!m->app_peer || m->app_peer[m->proc_host[k]] < 0 || m->app_peer[m->proc_host[k]] >= H))
+            return -22;
     }
-    if (any_udp) {   // the datagram processes' applications (shd_tcp_model's comment)
-        if (!m->app_spec || m->n_app_specs <= 0 || m->udp_payload < 1 || m->udp_payload > kDgramMax) return -22;
-        std::vector<uint8_t> seen(H, 0);
-        for (int32_t k = 0; k < P; k++) {
-            const int32_t a = app_of(k);
-            if (a < 0) continue;
-            if (a >= m->n_app_specs || seen[m->proc_host[k]]++) return -22;
-            const uint32_t* s = m->app_spec + 4 * (size_t)a;
-            if (s[0] > 2 || s[1] > 2 || s[3] > 1) return -22;
-            if (s[1] == 0 && !m->dest_cum) return -22;
-            if (s[1] == 1 && (!m->app_peer || m->app_peer[m->proc_host[k]] < 0 || m->app_peer[m->proc_host[k]] >= H))
-                return -22;
-        }
-        if (m->host_class && m->n_classes > 1)
-            for (int32_t a = 0; a < H; a++) if (m->host_class[a] >= m->n_classes) return -22;
-    }
-    // packet capture reads every packet's TCP header (network_interface.c:348):
-    // the reference asserts on a datagram there, so such a model is refused
-    bool any_pcap = false;
-    if (m->pcap_host)
-        for (int32_t a = 0; a < H; a++) any_pcap |= m->pcap_host[a] != 0;
-    if (any_pcap && (any_udp || m->pcap_ring > (1u << 24))) return -22;
-    // each host's own heartbeat interval (host.c's heartbeatInterval): a zero
-    // entry is refused, as shd_model.host_heartbeat's is (shd_eng_create)
-    if (m->host_heartbeat)
-        for (int32_t a = 0; a < H; a++)
-            if (m->host_heartbeat[a] == 0) return -22;
-    const int32_t V = pc ? pc->T : m->n_vertices;
-    std::vector<int32_t> hvi(H);   // each host's table index: the given one, or its attached index in the cache
-    for (int32_t a = 0; a < H; a++) {
-        if (pc) {
-            if (m->host_vertex[a] < 0 || m->host_vertex[a] >= pc->V || pc->h_att_index[m->host_vertex[a]] < 0) return -22;
-            hvi[a] = pc->h_att_index[m->host_vertex[a]];
-        } else {
-            if (m->host_vertex[a] < 0 || m->host_vertex[a] >= V) return -22;
-            hvi[a] = m->host_vertex[a];
-        }
-    }
-    const uint32_t pool_cap = m->packets_per_host ? m->packets_per_host : kPoolDefault;
-    if (pool_cap > (1u << 24)) return -22;
-    std::vector<int32_t> per_vertex(V, 0);
-    for (int32_t a = 0; a < H; a++) per_vertex[hvi[a]]++;
-    uint64_t W = ~0ull;
+    if (m->host_class && m->n_classes > 1)
+        for (int32_t a = 0; a < H; a++) if (m->host_class[a] >= m->n_classes) return -22;
+    return 0;
+}
+
+// the window, and the connections' routes (-113 for a pair without one)
+static int plan_window(const shd_tcp_model* m, TcpPlan& p) {
+    shd_pc* pc = m->path_cache;
+    const int32_t P = m->n_procs, V = p.V;
+    const std::vector<int32_t>& hvi = p.hvi;
+    p.W = ~0ull;
     if (!pc) {
         // a client whose server is unreachable: the reference's connect fails with
         // ECONNREFUSED (host.c:1224-1234, topology_isRoutable); the device
@@ -4075,34 +4049,88 @@ static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, s
         // (ceil, worker.c:293), over the vertex pairs some pair of distinct hosts
         // realizes (a vertex with itself only when two hosts share it)
         for (int32_t u = 0; u < V; u++) {
-            if (!per_vertex[u]) continue;
+            if (!p.per_vertex[u]) continue;
             for (int32_t v = 0; v < V; v++) {
-                if (!per_vertex[v] || (u == v && per_vertex[u] < 2)) continue;
+                if (!p.per_vertex[v] || (u == v && p.per_vertex[u] < 2)) continue;
                 const double l = m->path_lat_ms[(size_t)u * V + v];
                 if (l < 0) continue;
                 const uint64_t w = (uint64_t)ceil(l * (double)kMs);
-                if (w < W) W = w;
+                if (w < p.W) p.W = w;
             }
         }
-    } else {
-        // the same from the cache's device tables: either endpoint's row may
-        // serve a pair, so both count (the window only bounds the rounds)
-        std::vector<int32_t> conn;   // (client vertex, server vertex, same host, route required)
-        for (int32_t k = 0; k < P; k++)
-            if (m->proc_peer[k] >= 0) {
-                const int32_t hc = m->proc_host[k], hs = m->proc_host[m->proc_peer[k]];
-                conn.push_back(hvi[hc]); conn.push_back(hvi[hs]); conn.push_back(hc == hs ? 1 : 0); conn.push_back(1);
-            }
-        std::vector<uint8_t> occ;   // datagrams may go between any two hosts: every pair of their vertices bounds it
-        if (any_udp) {
-            occ.resize(V);
-            for (int32_t u = 0; u < V; u++) occ[u] = (uint8_t)std::min<int32_t>(per_vertex[u], 2);
-        }
-        const int rr = tcp_pc_prep(pc, conn, occ, &W);
-        if (rr) return rr;
+        return 0;
     }
-    if (W == 0) return -22;
-    if (W == ~0ull) W = m->end_time ? m->end_time : 1;
+    // the same from the cache's device tables: either endpoint's row may
+    // serve a pair, so both count (the window only bounds the rounds)
+    std::vector<int32_t> conn;   // (client vertex, server vertex, same host, route required)
+    for (int32_t k = 0; k < P; k++)
+        if (m->proc_peer[k] >= 0) {
+            const int32_t hc = m->proc_host[k], hs = m->proc_host[m->proc_peer[k]];
+            conn.push_back(hvi[hc]); conn.push_back(hvi[hs]); conn.push_back(hc == hs ? 1 : 0); conn.push_back(1);
+        }
+    std::vector<uint8_t> occ;   // datagrams may go between any two hosts: every pair of their vertices bounds it
+    if (p.any_udp) {
+        occ.resize(V);
+        for (int32_t u = 0; u < V; u++) occ[u] = (uint8_t)std::min<int32_t>(p.per_vertex[u], 2);
+    }
+    return tcp_pc_prep(pc, conn, occ, &p.W);
+}
+
+static int tcp_plan(const shd_tcp_model* m, int32_t world, int32_t me, TcpPlan& p) {
+    shd_pc* pc = m ? m->path_cache : nullptr;
+    if (!m || m->n_hosts <= 0 || m->n_hosts > (1 << 26) || m->n_procs < 0 || !m->host_ip || !m->host_seed || !m->bw_down_kibps ||
+        !m->bw_up_kibps || (!pc && (!m->path_lat_ms || !m->path_rel || m->n_vertices <= 0)) || !m->host_vertex ||
+        (m->n_procs && (!m->proc_host || !m->proc_start || !m->proc_peer)))
+        return -22;
+    // the flow time series samples flow records at an interval: the bit needs both
+    if ((m->options & SHD_TCP_OPT_SERIES) &&
+        (!(m->options & SHD_TCP_OPT_FLOWS) || !m->series_interval_us || m->series_cap > (int32_t)kSeriesCapMax))
+        return -22;
+    // path_cache mode: a built cache of an undirected graph (the directed
+    // lookup reruns rows, topology.c:1987-1990: not restated on the device)
+    if (pc && (!pc->built || pc->directed || (!pc->complete && !pc->d_row))) return -22;
+    const int32_t H = m->n_hosts, P = m->n_procs;
+    if (world > H || world > 64) return -22;   // (the group's per-engine tables hold 64)
+    p.world = world; p.me = me;
+    p.h0 = (int32_t)(((int64_t)me * H) / world);
+    p.nloc = (int32_t)(((int64_t)(me + 1) * H) / world) - p.h0;
+    for (int32_t k = 0; k < P; k++) {
+        if (m->proc_host[k] < 0 || m->proc_host[k] >= H) return -22;
+        if (m->proc_peer[k] >= P || (m->proc_peer[k] >= 0 && m->proc_peer[m->proc_peer[k]] >= 0)) return -22;
+        // a client's server runs the echo; a datagram process has no echo peer
+        if (m->proc_peer[k] >= 0 && proc_app_of(m, m->proc_peer[k]) >= 0) return -22;
+        if (proc_app_of(m, k) >= 0 && m->proc_peer[k] >= 0) return -22;
+        p.any_udp |= proc_app_of(m, k) >= 0;
+    }
+    if (p.any_udp) TRY(plan_datagram_apps(m));
+    // packet capture reads every packet's TCP header (network_interface.c:348):
+    // the reference asserts on a datagram there, so such a model is refused
+    if (m->pcap_host)
+        for (int32_t a = 0; a < H; a++) p.any_pcap |= m->pcap_host[a] != 0;
+    if (p.any_pcap && (p.any_udp || m->pcap_ring > (1u << 24))) return -22;
+    // each host's own heartbeat interval (host.c's heartbeatInterval): a zero
+    // entry is refused, as shd_model.host_heartbeat's is (shd_eng_create)
+    if (m->host_heartbeat)
+        for (int32_t a = 0; a < H; a++)
+            if (m->host_heartbeat[a] == 0) return -22;
+    p.V = pc ? pc->T : m->n_vertices;
+    p.hvi.resize(H);
+    for (int32_t a = 0; a < H; a++) {
+        if (pc) {
+            if (m->host_vertex[a] < 0 || m->host_vertex[a] >= pc->V || pc->h_att_index[m->host_vertex[a]] < 0) return -22;
+            p.hvi[a] = pc->h_att_index[m->host_vertex[a]];
+        } else {
+            if (m->host_vertex[a] < 0 || m->host_vertex[a] >= p.V) return -22;
+            p.hvi[a] = m->host_vertex[a];
+        }
+    }
+    p.pool_cap = m->packets_per_host ? m->packets_per_host : kPoolDefault;
+    if (p.pool_cap > (1u << 24)) return -22;
+    p.per_vertex.assign(p.V, 0);
+    for (int32_t a = 0; a < H; a++) p.per_vertex[p.hvi[a]]++;
+    TRY(plan_window(m, p));
+    if (p.W == 0) return -22;
+    if (p.W == ~0ull) p.W = m->end_time ? m->end_time : 1;
     // test_tcp.c's client takes its server's listening port when it connects
     // (its message queue); the device publishes a port where the server's bind
     // runs, and another lane -- or, on a group, another engine -- sees it from
@@ -4116,54 +4144,242 @@ static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, s
     for (int32_t k = 0; k < P; k++) {
         const int32_t s = m->proc_peer[k];
         if (s < 0 || m->proc_host[k] == m->proc_host[s]) continue;
-        if (m->proc_start[k] >= m->proc_start[s] && m->proc_start[k] - m->proc_start[s] < W) return -22;
+        if (m->proc_start[k] >= m->proc_start[s] && m->proc_start[k] - m->proc_start[s] < p.W) return -22;
     }
+    if (!tcp_host_slots(m, p.h0, p.nloc, p.so, p.hpo, p.hp, &p.max_procs)) return -22;
+    if (m->qdisc > 1) return -22;
+    // nothing below refuses
+    p.hb_min = m->heartbeat_interval ? m->heartbeat_interval : kSec;
+    if (m->host_heartbeat) {   // this engine's slice
+        p.hb_min = ~0ull;
+        for (int32_t i = 0; i < p.nloc; i++) p.hb_min = std::min<uint64_t>(p.hb_min, m->host_heartbeat[p.h0 + i]);
+    }
+    // host_of_ip's table: at most half full; an address's first host wins (host order)
+    uint32_t cap = 64;
+    while (cap < 2u * (uint32_t)H) cap <<= 1;
+    p.ipk.assign(cap, ~0ull);
+    p.ip_mask = cap - 1;
+    for (int32_t i = 0; i < H; i++) {
+        const uint32_t ip = m->host_ip[i];
+        uint32_t k = ip_slot(ip, p.ip_mask);
+        while (p.ipk[k] != ~0ull && (uint32_t)(p.ipk[k] >> 32) != ip) k = (k + 1) & p.ip_mask;
+        if (p.ipk[k] == ~0ull) p.ipk[k] = ((uint64_t)ip << 32) | (uint32_t)i;
+    }
+    return 0;
+}
 
-    int rc = 0;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kWsDevices) return -5;
-    TcpWs& ws = g_ws[dev];
-    std::unique_lock<std::mutex> ws_lock(ws.mu);
-    const bool ws_keep = g_ws_keep;
-    Glob g;
-    memset(&g, 0, sizeof(g));
-    std::vector<DHost> hh(nloc);
-    std::vector<DProc> pp(P > 0 ? P : 1);
-    std::vector<int32_t> hp, hpo, so;   // this engine's hosts: their processes and socket slots as ranges
-    TcpResultX* resx = (TcpResultX*)calloc(1, sizeof(TcpResultX));
-    shd_tcp_result* res = &resx->pub;   // (the struct's first member: freed through it)
-    const bool flows_on = (m->options & SHD_TCP_OPT_FLOWS) != 0;
-    uint32_t* d_fcnt = nullptr; uint32_t* d_foff = nullptr;
-    const bool paths_on = (m->options & SHD_TCP_OPT_PATHS) != 0;
-    uint32_t* d_pcnt = nullptr; uint32_t* d_poff = nullptr;
-    uint32_t pt_cap = 0;
-    const bool series_on = (m->options & SHD_TCP_OPT_SERIES) != 0;
+// what the rounds change on the host side: the control word as last copied,
+// the capture records and the samples drained so far
+struct TcpLive {
+    TCtl hctl;
+    TcpPcap pcp;
     TcpSeries ser;
-    uint32_t* d_smap = nullptr;
-    double* d_lat = nullptr; double* d_rel = nullptr;
-    uint32_t* d_spec = nullptr; int32_t* d_apeer = nullptr; double* d_cum = nullptr; uint8_t* d_cls = nullptr;
-    int32_t* d_hv = nullptr;
-    uint64_t* d_ipk = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+};
+
+// One run's hold on the device: the workspace (locked for the run), the
+// kernels' argument block, the stream and its graph, and the device pointers
+// the later phases need beside Glob's, per option.  close() releases all of it
+// (the destructor does for a run that returned early): a failed run frees the
+// whole workspace and its result, a successful one frees the workspace unless
+// it is kept.
+struct TcpRun {
+    TcpWs& ws;
+    std::unique_lock<std::mutex> lock;
+    const bool keep;
+    bool closed = false;
+    Glob g;   // complete at the end of setup; the rounds and the collectors read it
+    TcpResultX* resx = nullptr;   // the run's until it succeeds
     hipStream_t st = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
     hipGraph_t graph = nullptr;
     hipGraphExec_t gexec = nullptr;
-    TCtl hctl;
-    std::vector<uint64_t> ipk;
-    uint64_t rounds = 0;
-    std::vector<DHost> hout(nloc);
-    TcpPcap pcp;
-    int32_t* d_pslot = nullptr;
-    uint64_t* d_hbh = nullptr;
-    uint64_t hb_min = 0;   // the smallest heartbeat interval among this engine's hosts (node_k)
-    uint32_t* d_ipall = nullptr; uint64_t* d_bwu = nullptr; uint64_t* d_bwd = nullptr;
     uint32_t* d_sched = nullptr;   // the first-touch schedule (TcpSched), when it has entries
-    char* d_xrecv = nullptr; uint64_t* d_pmine = nullptr; uint64_t* d_pall = nullptr; uint32_t* d_xcnt = nullptr;
-    char* d_gmine = nullptr; char* d_gall = nullptr;
-    constexpr size_t kGatherMax = 1024;   // bytes one rank contributes to a control all-gather (<= 64 engines)
+    TcpLive live;
+    struct { uint32_t *cnt = nullptr, *off = nullptr; } flows;   // the gather's per-host counts and offsets
+    struct { uint32_t *cnt = nullptr, *off = nullptr; uint32_t cap = 0; } paths;   // the pair table's, and its entries
+    struct { uint32_t* map = nullptr; } series;   // the flow gather's slot map
+    struct {   // a group's exchange: received segments, port publications, counts, the control all-gather's words
+        char* recv = nullptr;
+        uint64_t *pmine = nullptr, *pall = nullptr;
+        uint32_t* cnt = nullptr;
+        char *gmine = nullptr, *gall = nullptr;
+    } xch;
+
+    explicit TcpRun(TcpWs& w) : ws(w), lock(w.mu), keep(g_ws_keep) {
+        memset(&g, 0, sizeof(g));
+        memset(&live.hctl, 0, sizeof(live.hctl));
+    }
+    ~TcpRun() { if (!closed) close(true); }   // (not copyable: the lock)
+
+    void close(bool failed) {
+        closed = true;
+        if (d_sched) (void)hipFree(d_sched);
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+        if (gexec) (void)hipGraphExecDestroy(gexec);
+        if (graph) (void)hipGraphDestroy(graph);
+        if (st) (void)hipStreamDestroy(st);
+        if (!keep || failed) ws_free_all(ws);   // a failed run leaves no workspace behind
+        lock.unlock();
+        if (failed && resx) shd_tcp_result_free(&resx->pub);
+    }
+
+    // a workspace slot of n elements; false: no device memory (WS_NEED)
+    template <class T>
+    bool alloc(int slot, T** d, size_t n) const { return ws_alloc(ws, slot, d, sizeof(T) * n) == hipSuccess; }
+    // workspace slot <- n elements of a host array
+    template <class T>
+    int put(int slot, T** d, const std::remove_const_t<T>* src, size_t n) const {
+        std::remove_const_t<T>* p = nullptr;
+        HCHECK(ws_alloc(ws, slot, &p, sizeof(T) * n));
+        if (n) HCHECK(hipMemcpy(p, src, sizeof(T) * n, hipMemcpyHostToDevice));
+        *d = p;
+        return 0;
+    }
+    // workspace slot of n elements, every byte zero (or `byte`)
+    template <class T>
+    int zero(int slot, T** d, size_t n, int byte = 0) const {
+        HCHECK(ws_alloc(ws, slot, d, sizeof(T) * n));
+        if (n) HCHECK(hipMemset(*d, byte, sizeof(T) * n));
+        return 0;
+    }
+};
+// these slots, or -12 with this message (the failed hipMalloc's sticky error cleared)
+#define WS_NEED(ok, ...) do { if (!(ok)) { (void)hipGetLastError(); fprintf(stderr, __VA_ARGS__); return -12; } } while (0)
+
+// one array of a result, n elements; -12 fails the run (shd_tcp_result_free copes with a partly filled result)
+template <class T>
+static int res_alloc(T** out, size_t n) {
+    *out = (T*)malloc(sizeof(T) * (n ? n : 1));
+    return *out ? 0 : -12;
+}
+
+// one host per lane, 64 per wave (16 per wave measured +4 % at 16 k hosts,
+// not kept)
+constexpr int kLaneThreads = 64;
+static int lane_blocks(const Glob& g) { return (g.nloc + kLaneThreads - 1) / kLaneThreads; }
+
+// Phase 2, setup: Glob and every device buffer behind it, each part by what it
+// sets up.  All of it runs on the null stream; setup_stream waits for it.
+
+// the model's scalars and per-host tables, the processes' ports and their publications
+static int setup_model(TcpRun& r, const shd_tcp_model* m, const TcpPlan& p, int32_t trace) {
+    Glob& g = r.g;
+    const int32_t H = m->n_hosts, P = m->n_procs;
+    g.H = H; g.P = P; g.W = p.W;
+    g.h0 = p.h0; g.nloc = p.nloc; g.world = p.world; g.me = p.me;
+    g.end_time = m->end_time; g.hb = m->heartbeat_interval ? m->heartbeat_interval : kSec;
+    g.boot_end = m->bootstrap_end;   // the same on every rank of a group
+    g.tcp_bytes = m->tcp_bytes; g.trace = (trace & SHD_TCP_TRACE_STATUS) ? 1 : 0;
+    g.stat_on = g.trace;   // (| 2 with flow records, | 4 with path records, | 8 with host records: setup_options)
+    g.recv_buf = m->recv_buf; g.send_buf = m->send_buf; g.tcp_window = m->tcp_window;
+    g.qdisc_rr = m->qdisc;
+    g.V = p.V; g.pool_cap = p.pool_cap;
+    g.ip_mask = p.ip_mask;
+    TRY(r.put(kWsIpAll, &g.ip_all, m->host_ip, (size_t)H));
+    TRY(r.put(kWsBwu, &g.bwu_all, m->bw_up_kibps, (size_t)H));
+    TRY(r.put(kWsBwd, &g.bwd_all, m->bw_down_kibps, (size_t)H));
+    TRY(r.put(kWsHv, &g.hv, p.hvi.data(), (size_t)H));
+    TRY(r.put(kWsIpk, &g.ip_key, p.ipk.data(), p.ipk.size()));
+    TRY(r.zero(kWsProcPort, &g.proc_port, (size_t)(P > 0 ? P : 1)));
+    {   // every engine sizes the publications alike: the most processes any engine's hosts run
+        std::vector<uint32_t> per(p.world, 0);
+        for (int32_t k = 0; k < P; k++) {
+            int32_t w = 0;
+            while (w + 1 < p.world && (int64_t)m->proc_host[k] >= ((int64_t)(w + 1) * H) / p.world) w++;
+            per[w]++;
+        }
+        g.pcap = 1;
+        for (uint32_t v : per) g.pcap = v > g.pcap ? v : g.pcap;
+    }
+    TRY(r.zero(kWsPortNew, &g.port_new, (size_t)g.pcap + 1));
+    g.nport_new = (uint32_t*)(g.port_new + g.pcap);
+    return 0;
+}
+
+// the datagram processes' applications
+static int setup_datagram_app(TcpRun& r, const shd_tcp_model* m) {
+    Glob& g = r.g;
+    const size_t H = (size_t)m->n_hosts;
+    g.udp_payload = m->udp_payload;
+    g.n_classes = m->n_classes;
+    const bool classes = m->host_class && m->n_classes > 1;
+    TRY(r.put(kWsAppSpec, &g.app_spec, m->app_spec, 4 * (size_t)m->n_app_specs));
+    if (m->app_peer) TRY(r.put(kWsAppPeer, &g.app_peer, m->app_peer, H));
+    if (m->dest_cum) TRY(r.put(kWsDestCum, &g.dest_cum, m->dest_cum, (size_t)(classes ? m->n_classes : 1) * H));
+    if (classes) TRY(r.put(kWsHostClass, &g.host_class, m->host_class, H));
+    return 0;
+}
+
+// the path tables, or the cache's tables and ranks (copied back at the end)
+// with the rounds' first-touch log and this call's schedule
+static int setup_paths(TcpRun& r, const shd_tcp_model* m, const TcpPlan& p, const TcpSched* sch) {
+    Glob& g = r.g;
+    shd_pc* pc = m->path_cache;
+    const size_t V = (size_t)p.V;
+    if (!pc) {
+        TRY(r.put(kWsLat, &g.lat, m->path_lat_ms, V * V));
+        TRY(r.put(kWsRel, &g.rel, m->path_rel, V * V));
+        return 0;
+    }
+    g.pcm = 1;
+    g.pT = p.V;
+    g.pc_complete = pc->complete ? 1u : 0u;
+    g.pc_prefer_direct = pc->prefer_direct ? 1u : 0u;
+    g.prow = pc->d_row; g.pself = pc->d_self; g.pdir = pc->d_dir; g.padj = pc->d_adj; g.pself_eid = pc->d_self_eid;
+    TRY(r.put(kWsRank, &g.rank, pc->h_rank, V));
+    TRY(r.put(kWsSrank, &g.srank, pc->h_self_rank, V));
+    TRY(r.put(kWsNextRank, &g.next_rank, &pc->next_rank, 1));
+    g.ft_cap = (uint32_t)m->n_hosts * 4u > (1u << 16) ? (uint32_t)m->n_hosts * 4u : (1u << 16);   // (a group's: every engine's log)
+    HCHECK(ws_alloc(r.ws, kWsFt, &g.ft, sizeof(shd_tcp_query) * (size_t)g.ft_cap));
+    HCHECK(ws_alloc(r.ws, kWsFtord, &g.ftord, sizeof(int32_t) * (size_t)g.ft_cap));
+    TRY(r.zero(kWsNft, &g.nft, 1));
+    if (sch && !sch->round.empty() && p.world == 1) {
+        const size_t nr = sch->round.size(), nv = sch->v.size();
+        HCHECK(hipMalloc((void**)&r.d_sched, sizeof(uint32_t) * (2 * nr + 1) + sizeof(int32_t) * (nv ? nv : 1)));
+        HCHECK(hipMemcpy(r.d_sched, sch->round.data(), sizeof(uint32_t) * nr, hipMemcpyHostToDevice));
+        HCHECK(hipMemcpy(r.d_sched + nr, sch->off.data(), sizeof(uint32_t) * (nr + 1), hipMemcpyHostToDevice));
+        if (nv) HCHECK(hipMemcpy(r.d_sched + 2 * nr + 1, sch->v.data(), sizeof(int32_t) * nv, hipMemcpyHostToDevice));
+        g.sched_round = r.d_sched;
+        g.sched_off = r.d_sched + nr;
+        g.sched_v = (const int32_t*)(r.d_sched + 2 * nr + 1);
+        g.sched_n = (uint32_t)nr;
+    }
+    return 0;
+}
+
+// a group's exchange: the segments (SHD_TCP_XCAP: deliveries per engine pair
+// and round), the port publications and the control all-gather's words
+constexpr size_t kGatherMax = 1024;   // bytes one rank contributes to a control all-gather (<= 64 engines)
+static int setup_exchange(TcpRun& r) {
+    Glob& g = r.g;
+    const size_t world = (size_t)g.world;
+    g.xcap = (uint32_t)std::max<int64_t>(16384, 8 * (int64_t)g.nloc);
+    if (const char* e = getenv("SHD_TCP_XCAP")) {
+        const long v = strtol(e, nullptr, 10);
+        if (v >= 16 && v <= (1l << 22)) g.xcap = (uint32_t)v;
+    }
+    g.xsack_cap = g.xcap * kMailSack;
+    g.xseg = sizeof(XSegHead) + (size_t)g.xcap * sizeof(Mail) + (size_t)g.xsack_cap * sizeof(int32_t);
+    g.xseg = (g.xseg + 255) & ~(size_t)255;
+    TRY(r.zero(kWsXsend, &g.xsend, g.xseg * world));
+    HCHECK(ws_alloc(r.ws, kWsXrecv, &r.xch.recv, g.xseg * world));
+    HCHECK(ws_alloc(r.ws, kWsPmine, &r.xch.pmine, sizeof(uint64_t) * (1 + g.pcap)));
+    HCHECK(ws_alloc(r.ws, kWsPall, &r.xch.pall, sizeof(uint64_t) * (1 + g.pcap) * world));
+    HCHECK(ws_alloc(r.ws, kWsXcnt, &r.xch.cnt, sizeof(uint32_t) * (4 * world + 2)));
+    HCHECK(ws_alloc(r.ws, kWsGmine, &r.xch.gmine, kGatherMax));
+    HCHECK(ws_alloc(r.ws, kWsGall, &r.xch.gall, kGatherMax * world));
+    return 0;
+}
+
+// the hosts and processes as the device starts them, the socket slots and their directory
+static int setup_hosts(TcpRun& r, const shd_tcp_model* m, const TcpPlan& p) {
+    Glob& g = r.g;
+    const int32_t P = m->n_procs, nloc = p.nloc;
+    std::vector<DHost> hh(nloc);
     for (int32_t i = 0; i < nloc; i++) {
         DHost& x = hh[i];
-        const int32_t gi = h0 + i;
+        const int32_t gi = p.h0 + i;
         memset(&x, 0, sizeof(x));
         x.ip = m->host_ip[gi];
         x.rng = m->host_seed[gi];
@@ -4173,718 +4389,639 @@ static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, s
         x.rx_refill = m->bw_down_kibps[gi] * 1024 / 1000;
         x.tx_cap = x.tx_refill + kMTU;
         x.rx_cap = x.rx_refill + kMTU;
-        x.nfree = pool_cap;
+        x.nfree = p.pool_cap;
         x.next_handle = 3;
     }
+    std::vector<DProc> pp(P > 0 ? P : 1);
     for (int32_t k = 0; k < P; k++) {
         DProc& pr = pp[k];
         memset(&pr, 0, sizeof(pr));
         pr.host = m->proc_host[k]; pr.index = k; pr.peer = m->proc_peer[k]; pr.start = m->proc_start[k];
         pr.fd = pr.listenfd = pr.wait_fd = -1;
-        pr.app = app_of(k);
+        pr.app = proc_app_of(m, k);
     }
-    {
-        uint32_t mp = 0;
-        if (!tcp_host_slots(m, h0, nloc, so, hpo, hp, &mp)) { free(res); return -22; }
-        res->max_host_procs = mp;
-        res->sock_bytes = sizeof(DSock) * (uint64_t)so[nloc];
-    }
+    const size_t ns = (size_t)p.so[nloc];
+    TRY(r.put(kWsHost, &g.host, hh.data(), (size_t)nloc));
+    TRY(r.zero(kWsSock, &g.sock, ns));
+    TRY(r.put(kWsSockOff, &g.sock_off, p.so.data(), p.so.size()));
+    TRY(r.zero(kWsDir, &g.dir, ns + kDirPad));
+    HCHECK(ws_alloc(r.ws, kWsIfq, &g.ifq, sizeof(int32_t) * ns));
+    TRY(r.put(kWsProcOff, &g.proc_off, p.hpo.data(), p.hpo.size()));
+    TRY(r.put(kWsProc, &g.proc, pp.data(), pp.size()));
+    TRY(r.put(kWsHostProcs, &g.host_procs, p.hp.data(), p.hp.size()));
+    return 0;
+}
 
-    {   // host_of_ip's table: at most half full; an address's first host wins (host order)
-        uint32_t cap = 64;
-        while (cap < 2u * (uint32_t)H) cap <<= 1;
-        ipk.assign(cap, ~0ull);
-        g.ip_mask = cap - 1;
-        for (int32_t i = 0; i < H; i++) {
-            const uint32_t ip = m->host_ip[i];
-            uint32_t k = ip_slot(ip, g.ip_mask);
-            while (ipk[k] != ~0ull && (uint32_t)(ipk[k] >> 32) != ip) k = (k + 1) & g.ip_mask;
-            if (ipk[k] == ~0ull) ipk[k] = ((uint64_t)ip << 32) | (uint32_t)i;
-        }
+// the option blocks (shd_tcp_model.options): flow records, their time series, path records, host records
+static int setup_options(TcpRun& r, const shd_tcp_model* m, const TcpPlan& p) {
+    Glob& g = r.g;
+    const size_t ns = (size_t)p.so[p.nloc], nloc = (size_t)p.nloc;
+    if (m->options & SHD_TCP_OPT_FLOWS) {   // a record beside every slot, and the gather's per-host counts and offsets
+        WS_NEED(r.alloc(kWsFlow, &g.flow, ns) && r.alloc(kWsFlowCnt, &r.flows.cnt, nloc) &&
+                    r.alloc(kWsFlowOff, &r.flows.off, nloc + 1),
+                "shd_tcp_run: no device memory for the flow records of %zu socket slots\n", ns);
+        HCHECK(hipMemset(g.flow, 0, sizeof(DFlow) * ns));
+        g.flow_on = 1;
+        g.stat_on |= 2u;
     }
-    g.H = H; g.P = P; g.W = W;
-    g.h0 = h0; g.nloc = nloc; g.world = world; g.me = me;
-    g.end_time = m->end_time; g.hb = m->heartbeat_interval ? m->heartbeat_interval : kSec;
-    g.boot_end = m->bootstrap_end;   // the same on every rank of a group
-    hb_min = g.hb;
-    if (m->host_heartbeat) {   // this engine's slice
-        hb_min = ~0ull;
-        for (int32_t i = 0; i < nloc; i++) hb_min = std::min<uint64_t>(hb_min, m->host_heartbeat[h0 + i]);
+    if (m->options & SHD_TCP_OPT_SERIES) {   // the engine's sample array and its counter, a boundary per host, the gather's slot map
+        g.ser_cap = m->series_cap > 0 ? (uint32_t)m->series_cap
+                                      : (uint32_t)std::min<uint64_t>(std::max<uint64_t>(kSeriesCapMin, kSeriesPerSlot * (uint64_t)ns),
+                                                                     kSeriesCapMax);
+        g.ser_ival = 1000ull * m->series_interval_us;
+        WS_NEED(r.alloc(kWsSer, &g.ser, (size_t)g.ser_cap) && r.alloc(kWsNser, &g.nser, 1) &&
+                    r.alloc(kWsSerNext, &g.ser_next, nloc) && r.alloc(kWsSerMap, &r.series.map, ns),
+                "shd_tcp_run: no device memory for the flow time series (%u samples, %.1f GB); "
+                "set a smaller series_cap\n", g.ser_cap, sizeof(shd_tcp_sample) * (double)g.ser_cap / 1e9);
+        HCHECK(hipMemset(g.nser, 0, sizeof(uint32_t)));
+        k_tcp_series_init<<<(unsigned)((nloc + 255) / 256), 256>>>(g.ser_next, p.nloc, g.ser_ival);
+        HCHECK(hipGetLastError());
+        g.ser_on = 1;
     }
-    g.tcp_bytes = m->tcp_bytes; g.trace = (trace & SHD_TCP_TRACE_STATUS) ? 1 : 0;
-    g.stat_on = g.trace;   // (| 2 with flow records, below)
-    g.recv_buf = m->recv_buf; g.send_buf = m->send_buf; g.tcp_window = m->tcp_window;
-    if (m->qdisc > 1) { free(res); return -22; }
-    g.qdisc_rr = m->qdisc;
-    if (any_udp) {
-        g.udp_payload = m->udp_payload;
-        g.n_classes = m->n_classes;
-        const size_t ncum = (size_t)(m->host_class && m->n_classes > 1 ? m->n_classes : 1) * (size_t)H;
-        HCHECK(ws_alloc(ws, kWsAppSpec, &d_spec, sizeof(uint32_t) * 4 * (size_t)m->n_app_specs));
-        HCHECK(hipMemcpy(d_spec, m->app_spec, sizeof(uint32_t) * 4 * (size_t)m->n_app_specs, hipMemcpyHostToDevice));
-        g.app_spec = d_spec;
-        if (m->app_peer) {
-            HCHECK(ws_alloc(ws, kWsAppPeer, &d_apeer, sizeof(int32_t) * (size_t)H));
-            HCHECK(hipMemcpy(d_apeer, m->app_peer, sizeof(int32_t) * (size_t)H, hipMemcpyHostToDevice));
-            g.app_peer = d_apeer;
-        }
-        if (m->dest_cum) {
-            HCHECK(ws_alloc(ws, kWsDestCum, &d_cum, sizeof(double) * ncum));
-            HCHECK(hipMemcpy(d_cum, m->dest_cum, sizeof(double) * ncum, hipMemcpyHostToDevice));
-            g.dest_cum = d_cum;
-        }
-        if (m->host_class && m->n_classes > 1) {
-            HCHECK(ws_alloc(ws, kWsHostClass, &d_cls, (size_t)H));
-            HCHECK(hipMemcpy(d_cls, m->host_class, (size_t)H, hipMemcpyHostToDevice));
-            g.host_class = d_cls;
-        }
+    if (m->options & SHD_TCP_OPT_PATHS) {   // an accumulator beside every slot, the pair table, and the gather's flags and offsets
+        const uint32_t cap = r.paths.cap = tcp_path_slots(m, p.hvi);
+        WS_NEED(r.alloc(kWsPacc, &g.pacc, ns) && r.alloc(kWsPtab, &g.ptab, (size_t)cap) && r.alloc(kWsPtFull, &g.pt_full, 1) &&
+                    r.alloc(kWsPtCnt, &r.paths.cnt, (size_t)cap) && r.alloc(kWsPtOff, &r.paths.off, (size_t)cap + 1),
+                "shd_tcp_run: no device memory for the path records (%zu socket slots, %u pairs)\n", ns, cap);
+        HCHECK(hipMemset(g.pacc, 0, sizeof(DPath) * ns));
+        HCHECK(hipMemset(g.pt_full, 0, sizeof(uint32_t)));
+        k_tcp_path_init<<<(cap + 255) / 256, 256>>>(g.ptab, cap);
+        HCHECK(hipGetLastError());
+        g.pt_mask = cap - 1;
+        g.path_on = 1;
+        g.stat_on |= 4u;
     }
-    if (!pc) {
-        HCHECK(ws_alloc(ws, kWsLat, &d_lat, sizeof(double) * (size_t)V * V));
-        HCHECK(ws_alloc(ws, kWsRel, &d_rel, sizeof(double) * (size_t)V * V));
-        HCHECK(hipMemcpy(d_lat, m->path_lat_ms, sizeof(double) * (size_t)V * V, hipMemcpyHostToDevice));
-        HCHECK(hipMemcpy(d_rel, m->path_rel, sizeof(double) * (size_t)V * V, hipMemcpyHostToDevice));
-    } else {   // the cache's tables and ranks (copied back at the end)
-        g.pcm = 1;
-        g.pT = V;
-        g.pc_complete = pc->complete ? 1u : 0u;
-        g.pc_prefer_direct = pc->prefer_direct ? 1u : 0u;
-        g.prow = pc->d_row; g.pself = pc->d_self; g.pdir = pc->d_dir; g.padj = pc->d_adj; g.pself_eid = pc->d_self_eid;
-        HCHECK(ws_alloc(ws, kWsRank, &g.rank, sizeof(int32_t) * (size_t)V));
-        HCHECK(ws_alloc(ws, kWsSrank, &g.srank, sizeof(int32_t) * (size_t)V));
-        HCHECK(ws_alloc(ws, kWsNextRank, &g.next_rank, sizeof(int32_t)));
-        HCHECK(hipMemcpy(g.rank, pc->h_rank, sizeof(int32_t) * (size_t)V, hipMemcpyHostToDevice));
-        HCHECK(hipMemcpy(g.srank, pc->h_self_rank, sizeof(int32_t) * (size_t)V, hipMemcpyHostToDevice));
-        HCHECK(hipMemcpy(g.next_rank, &pc->next_rank, sizeof(int32_t), hipMemcpyHostToDevice));
-        g.ft_cap = (uint32_t)H * 4u > (1u << 16) ? (uint32_t)H * 4u : (1u << 16);   // (a group's: every engine's log)
-        HCHECK(ws_alloc(ws, kWsFt, &g.ft, sizeof(shd_tcp_query) * (size_t)g.ft_cap));
-        HCHECK(ws_alloc(ws, kWsFtord, &g.ftord, sizeof(int32_t) * (size_t)g.ft_cap));
-        HCHECK(ws_alloc(ws, kWsNft, &g.nft, sizeof(uint32_t)));
-        HCHECK(hipMemset(g.nft, 0, sizeof(uint32_t)));
-        if (sch && !sch->round.empty() && world == 1) {
-            const size_t nr = sch->round.size(), nv = sch->v.size();
-            HCHECK(hipMalloc((void**)&d_sched, sizeof(uint32_t) * (2 * nr + 1) + sizeof(int32_t) * (nv ? nv : 1)));
-            HCHECK(hipMemcpy(d_sched, sch->round.data(), sizeof(uint32_t) * nr, hipMemcpyHostToDevice));
-            HCHECK(hipMemcpy(d_sched + nr, sch->off.data(), sizeof(uint32_t) * (nr + 1), hipMemcpyHostToDevice));
-            if (nv) HCHECK(hipMemcpy(d_sched + 2 * nr + 1, sch->v.data(), sizeof(int32_t) * nv, hipMemcpyHostToDevice));
-            g.sched_round = d_sched;
-            g.sched_off = d_sched + nr;
-            g.sched_v = (const int32_t*)(d_sched + 2 * nr + 1);
-            g.sched_n = (uint32_t)nr;
-        }
+    if (m->options & SHD_TCP_OPT_HOSTS) {   // a record per local host, zero at the start of every run (a rerun's too)
+        WS_NEED(r.alloc(kWsHrec, &g.hrec, nloc), "shd_tcp_run: no device memory for the host records of %d hosts\n", p.nloc);
+        HCHECK(hipMemset(g.hrec, 0, sizeof(shd_tcp_hostrec) * nloc));
+        g.stat_on |= 8u;
     }
-    HCHECK(ws_alloc(ws, kWsIpAll, &d_ipall, sizeof(uint32_t) * (size_t)H));
-    HCHECK(hipMemcpy(d_ipall, m->host_ip, sizeof(uint32_t) * (size_t)H, hipMemcpyHostToDevice));
-    HCHECK(ws_alloc(ws, kWsBwu, &d_bwu, sizeof(uint64_t) * (size_t)H));
-    HCHECK(hipMemcpy(d_bwu, m->bw_up_kibps, sizeof(uint64_t) * (size_t)H, hipMemcpyHostToDevice));
-    HCHECK(ws_alloc(ws, kWsBwd, &d_bwd, sizeof(uint64_t) * (size_t)H));
-    HCHECK(hipMemcpy(d_bwd, m->bw_down_kibps, sizeof(uint64_t) * (size_t)H, hipMemcpyHostToDevice));
-    g.ip_all = d_ipall; g.bwu_all = d_bwu; g.bwd_all = d_bwd;
-    HCHECK(ws_alloc(ws, kWsProcPort, &g.proc_port, sizeof(uint32_t) * pp.size()));
-    HCHECK(hipMemset(g.proc_port, 0, sizeof(uint32_t) * pp.size()));
-    {   // every engine sizes the publications alike: the most processes any engine's hosts run
-        std::vector<uint32_t> per(world, 0);
-        for (int32_t k = 0; k < P; k++) {
-            int32_t r = 0;
-            while (r + 1 < world && (int64_t)m->proc_host[k] >= ((int64_t)(r + 1) * H) / world) r++;
-            per[r]++;
-        }
-        g.pcap = 1;
-        for (uint32_t v : per) g.pcap = v > g.pcap ? v : g.pcap;
-    }
-    HCHECK(ws_alloc(ws, kWsPortNew, &g.port_new, sizeof(uint64_t) * (g.pcap + 1)));
-    g.nport_new = (uint32_t*)(g.port_new + g.pcap);
-    HCHECK(hipMemset(g.port_new, 0, sizeof(uint64_t) * (g.pcap + 1)));
-    if (world > 1) {   // the exchange's segments (SHD_TCP_XCAP: deliveries per engine pair and round)
-        g.xcap = (uint32_t)std::max<int64_t>(16384, 8 * (int64_t)nloc);
-        if (const char* e = getenv("SHD_TCP_XCAP")) {
-            const long v = strtol(e, nullptr, 10);
-            if (v >= 16 && v <= (1l << 22)) g.xcap = (uint32_t)v;
-        }
-        g.xsack_cap = g.xcap * kMailSack;
-        g.xseg = sizeof(XSegHead) + (size_t)g.xcap * sizeof(Mail) + (size_t)g.xsack_cap * sizeof(int32_t);
-        g.xseg = (g.xseg + 255) & ~(size_t)255;
-        HCHECK(ws_alloc(ws, kWsXsend, &g.xsend, g.xseg * (size_t)world));
-        HCHECK(ws_alloc(ws, kWsXrecv, &d_xrecv, g.xseg * (size_t)world));
-        HCHECK(hipMemset(g.xsend, 0, g.xseg * (size_t)world));
-        HCHECK(ws_alloc(ws, kWsPmine, &d_pmine, sizeof(uint64_t) * (1 + g.pcap)));
-        HCHECK(ws_alloc(ws, kWsPall, &d_pall, sizeof(uint64_t) * (1 + g.pcap) * (size_t)world));
-        HCHECK(ws_alloc(ws, kWsXcnt, &d_xcnt, sizeof(uint32_t) * (4 * (size_t)world + 2)));
-        HCHECK(ws_alloc(ws, kWsGmine, &d_gmine, kGatherMax));
-        HCHECK(ws_alloc(ws, kWsGall, &d_gall, kGatherMax * (size_t)world));
-    }
-    HCHECK(ws_alloc(ws, kWsHv, &d_hv, sizeof(int32_t) * (size_t)H));
-    HCHECK(hipMemcpy(d_hv, hvi.data(), sizeof(int32_t) * (size_t)H, hipMemcpyHostToDevice));
-    g.lat = d_lat; g.rel = d_rel; g.hv = d_hv; g.V = V; g.pool_cap = pool_cap;
-    HCHECK(ws_alloc(ws, kWsHost, &g.host, sizeof(DHost) * nloc));
-    HCHECK(hipMemcpy(g.host, hh.data(), sizeof(DHost) * nloc, hipMemcpyHostToDevice));
-    {
-        const size_t ns = (size_t)so[nloc];
-        int32_t *d_so = nullptr, *d_hpo = nullptr;
-        HCHECK(ws_alloc(ws, kWsSock, &g.sock, sizeof(DSock) * ns));
-        HCHECK(hipMemset(g.sock, 0, sizeof(DSock) * ns));
-        HCHECK(ws_alloc(ws, kWsSockOff, &d_so, sizeof(int32_t) * so.size()));
-        HCHECK(hipMemcpy(d_so, so.data(), sizeof(int32_t) * so.size(), hipMemcpyHostToDevice));
-        g.sock_off = d_so;
-        HCHECK(ws_alloc(ws, kWsDir, &g.dir, sizeof(DKey) * (ns + kDirPad)));
-        HCHECK(hipMemset(g.dir, 0, sizeof(DKey) * (ns + kDirPad)));
-        HCHECK(ws_alloc(ws, kWsIfq, &g.ifq, sizeof(int32_t) * ns));
-        if (flows_on) {   // a record beside every slot, and the gather's per-host counts and offsets
-            if (ws_alloc(ws, kWsFlow, &g.flow, sizeof(DFlow) * ns) != hipSuccess ||
-                ws_alloc(ws, kWsFlowCnt, &d_fcnt, sizeof(uint32_t) * (size_t)nloc) != hipSuccess ||
-                ws_alloc(ws, kWsFlowOff, &d_foff, sizeof(uint32_t) * ((size_t)nloc + 1)) != hipSuccess) {
-                (void)hipGetLastError();
-                fprintf(stderr, "shd_tcp_run: no device memory for the flow records of %zu socket slots\n", ns);
-                rc = -12;
-                goto done;
-            }
-            HCHECK(hipMemset(g.flow, 0, sizeof(DFlow) * ns));
-            g.flow_on = 1;
-            g.stat_on |= 2u;
-        }
-        if (series_on) {   // the engine's sample array and its counter, a boundary per host, the gather's slot map
-            g.ser_cap = m->series_cap > 0 ? (uint32_t)m->series_cap
-                                          : (uint32_t)std::min<uint64_t>(std::max<uint64_t>(kSeriesCapMin, kSeriesPerSlot * (uint64_t)ns),
-                                                                         kSeriesCapMax);
-            g.ser_ival = 1000ull * m->series_interval_us;
-            if (ws_alloc(ws, kWsSer, &g.ser, sizeof(shd_tcp_sample) * (size_t)g.ser_cap) != hipSuccess ||
-                ws_alloc(ws, kWsNser, &g.nser, sizeof(uint32_t)) != hipSuccess ||
-                ws_alloc(ws, kWsSerNext, &g.ser_next, sizeof(uint64_t) * (size_t)nloc) != hipSuccess ||
-                ws_alloc(ws, kWsSerMap, &d_smap, sizeof(uint32_t) * ns) != hipSuccess) {
-                (void)hipGetLastError();
-                fprintf(stderr, "shd_tcp_run: no device memory for the flow time series (%u samples, %.1f GB); "
-                                "set a smaller series_cap\n", g.ser_cap, sizeof(shd_tcp_sample) * (double)g.ser_cap / 1e9);
-                rc = -12;
-                goto done;
-            }
-            HCHECK(hipMemset(g.nser, 0, sizeof(uint32_t)));
-            k_tcp_series_init<<<(unsigned)((nloc + 255) / 256), 256>>>(g.ser_next, nloc, g.ser_ival);
-            HCHECK(hipGetLastError());
-            g.ser_on = 1;
-        }
-        if (paths_on) {   // an accumulator beside every slot, the pair table, and the gather's flags and offsets
-            pt_cap = tcp_path_slots(m, hvi);
-            if (ws_alloc(ws, kWsPacc, &g.pacc, sizeof(DPath) * ns) != hipSuccess ||
-                ws_alloc(ws, kWsPtab, &g.ptab, sizeof(PEnt) * (size_t)pt_cap) != hipSuccess ||
-                ws_alloc(ws, kWsPtFull, &g.pt_full, sizeof(uint32_t)) != hipSuccess ||
-                ws_alloc(ws, kWsPtCnt, &d_pcnt, sizeof(uint32_t) * (size_t)pt_cap) != hipSuccess ||
-                ws_alloc(ws, kWsPtOff, &d_poff, sizeof(uint32_t) * ((size_t)pt_cap + 1)) != hipSuccess) {
-                (void)hipGetLastError();
-                fprintf(stderr, "shd_tcp_run: no device memory for the path records (%zu socket slots, %u pairs)\n", ns,
-                        pt_cap);
-                rc = -12;
-                goto done;
-            }
-            HCHECK(hipMemset(g.pacc, 0, sizeof(DPath) * ns));
-            HCHECK(hipMemset(g.pt_full, 0, sizeof(uint32_t)));
-            k_tcp_path_init<<<(pt_cap + 255) / 256, 256>>>(g.ptab, pt_cap);
-            HCHECK(hipGetLastError());
-            g.pt_mask = pt_cap - 1;
-            g.path_on = 1;
-            g.stat_on |= 4u;
-        }
-        if (m->options & SHD_TCP_OPT_HOSTS) {   // a record per local host, zero at the start of every run (a rerun's too)
-            if (ws_alloc(ws, kWsHrec, &g.hrec, sizeof(shd_tcp_hostrec) * (size_t)nloc) != hipSuccess) {
-                (void)hipGetLastError();
-                fprintf(stderr, "shd_tcp_run: no device memory for the host records of %d hosts\n", nloc);
-                rc = -12;
-                goto done;
-            }
-            HCHECK(hipMemset(g.hrec, 0, sizeof(shd_tcp_hostrec) * (size_t)nloc));
-            g.stat_on |= 8u;
-        }
-        HCHECK(ws_alloc(ws, kWsProcOff, &d_hpo, sizeof(int32_t) * hpo.size()));
-        HCHECK(hipMemcpy(d_hpo, hpo.data(), sizeof(int32_t) * hpo.size(), hipMemcpyHostToDevice));
-        g.proc_off = d_hpo;
-    }
-    HCHECK(ws_alloc(ws, kWsProc, &g.proc, sizeof(DProc) * pp.size()));
-    HCHECK(hipMemcpy(g.proc, pp.data(), sizeof(DProc) * pp.size(), hipMemcpyHostToDevice));
-    {
-        int32_t* d_hp = nullptr;
-        HCHECK(ws_alloc(ws, kWsHostProcs, &d_hp, sizeof(int32_t) * hp.size()));
-        if (!hp.empty()) HCHECK(hipMemcpy(d_hp, hp.data(), sizeof(int32_t) * hp.size(), hipMemcpyHostToDevice));
-        g.host_procs = d_hp;
-    }
-    HCHECK(ws_alloc(ws, kWsPool, &g.pool, sizeof(DPkt) * (size_t)nloc * pool_cap));
-    HCHECK(ws_alloc(ws, kWsPsack, &g.psack, sizeof(int32_t) * kPktSack * (size_t)nloc * pool_cap));
-    HCHECK(ws_alloc(ws, kWsFreel, &g.freel, sizeof(int32_t) * (size_t)nloc * pool_cap));
-    k_tcp_free_init<<<(unsigned)(((size_t)nloc * pool_cap + 255) / 256), 256>>>(g.freel, (size_t)nloc * pool_cap, pool_cap);
+    return 0;
+}
+
+// the packet pools, event heaps, CoDel queues, the two mailboxes and the control word
+static int setup_packets(TcpRun& r) {
+    Glob& g = r.g;
+    const size_t nloc = (size_t)g.nloc, npool = nloc * g.pool_cap;
+    HCHECK(ws_alloc(r.ws, kWsPool, &g.pool, sizeof(DPkt) * npool));
+    HCHECK(ws_alloc(r.ws, kWsPsack, &g.psack, sizeof(int32_t) * kPktSack * npool));
+    HCHECK(ws_alloc(r.ws, kWsFreel, &g.freel, sizeof(int32_t) * npool));
+    k_tcp_free_init<<<(unsigned)((npool + 255) / 256), 256>>>(g.freel, npool, g.pool_cap);
     HCHECK(hipGetLastError());
-    HCHECK(ws_alloc(ws, kWsEv, &g.ev, sizeof(DEv) * (size_t)nloc * kEv));
-    HCHECK(ws_alloc(ws, kWsCq, &g.cq, sizeof(CqEnt) * (size_t)nloc * kCq));
-    {
-        const uint32_t parts = (uint32_t)nloc * 32u > kMailMin ? (uint32_t)nloc * 32u : kMailMin;
-        g.mail_part = parts / kMailSub;
-        uint32_t ovf = g.mail_part * kMailSub / 2;
-        // SHD_TCP_MAIL_PART: smaller parts (the same overflow range), so that a
-        // test's model of a few hundred hosts exercises the overflow path
-        if (const char* e = getenv("SHD_TCP_MAIL_PART")) {
-            const long v = strtol(e, nullptr, 10);
-            if (v >= 1 && v < (long)g.mail_part) g.mail_part = (uint32_t)v;
-        }
-        g.mail_cap = g.mail_part * kMailSub + ovf;
-        g.mail_stride = g.mail_cap + (world > 1 ? (uint32_t)world * g.xcap : 0u);
+    HCHECK(ws_alloc(r.ws, kWsEv, &g.ev, sizeof(DEv) * nloc * kEv));
+    HCHECK(ws_alloc(r.ws, kWsCq, &g.cq, sizeof(CqEnt) * nloc * kCq));
+    const uint32_t parts = (uint32_t)g.nloc * 32u > kMailMin ? (uint32_t)g.nloc * 32u : kMailMin;
+    g.mail_part = parts / kMailSub;
+    const uint32_t ovf = g.mail_part * kMailSub / 2;
+    // SHD_TCP_MAIL_PART: smaller parts (the same overflow range), so that a
+    // test's model of a few hundred hosts exercises the overflow path
+    if (const char* e = getenv("SHD_TCP_MAIL_PART")) {
+        const long v = strtol(e, nullptr, 10);
+        if (v >= 1 && v < (long)g.mail_part) g.mail_part = (uint32_t)v;
     }
+    g.mail_cap = g.mail_part * kMailSub + ovf;
+    g.mail_stride = g.mail_cap + (g.world > 1 ? (uint32_t)g.world * g.xcap : 0u);
     g.msack_cap = g.mail_cap * kMailSack;
-    HCHECK(ws_alloc(ws, kWsMsack, &g.msack, sizeof(int32_t) * 2 * (size_t)g.msack_cap));
-    HCHECK(ws_alloc(ws, kWsNmsack, &g.nmsack, sizeof(uint32_t) * 2));
-    HCHECK(hipMemset(g.nmsack, 0, sizeof(uint32_t) * 2));
-    HCHECK(ws_alloc(ws, kWsMail, &g.mail, sizeof(Mail) * 2 * (size_t)g.mail_stride));
-    HCHECK(ws_alloc(ws, kWsNmail, &g.nmail, sizeof(uint32_t) * 2 * (kMailSub + 1)));
-    HCHECK(hipMemset(g.nmail, 0, sizeof(uint32_t) * 2 * (kMailSub + 1)));
-    HCHECK(ws_alloc(ws, kWsMhead, &g.mhead, sizeof(int32_t) * 2 * (size_t)nloc));
-    HCHECK(hipMemset(g.mhead, 0xff, sizeof(int32_t) * 2 * (size_t)nloc));
-    HCHECK(ws_alloc(ws, kWsMnext, &g.mnext, sizeof(int32_t) * 2 * (size_t)g.mail_stride));
-    HCHECK(ws_alloc(ws, kWsCtl, &g.ctl, sizeof(TCtl)));
-    HCHECK(hipMemset(g.ctl, 0, sizeof(TCtl)));
-    HCHECK(ws_alloc(ws, kWsIpk, &d_ipk, sizeof(uint64_t) * ipk.size()));
-    HCHECK(hipMemcpy(d_ipk, ipk.data(), sizeof(uint64_t) * ipk.size(), hipMemcpyHostToDevice));
-    g.ip_key = d_ipk;
+    HCHECK(ws_alloc(r.ws, kWsMsack, &g.msack, sizeof(int32_t) * 2 * (size_t)g.msack_cap));
+    TRY(r.zero(kWsNmsack, &g.nmsack, 2));
+    HCHECK(ws_alloc(r.ws, kWsMail, &g.mail, sizeof(Mail) * 2 * (size_t)g.mail_stride));
+    TRY(r.zero(kWsNmail, &g.nmail, 2 * (kMailSub + 1)));
+    TRY(r.zero(kWsMhead, &g.mhead, 2 * nloc, 0xff));
+    HCHECK(ws_alloc(r.ws, kWsMnext, &g.mnext, sizeof(int32_t) * 2 * (size_t)g.mail_stride));
+    TRY(r.zero(kWsCtl, &g.ctl, 1));
+    TRY(r.zero(kWsNextTime, &g.next_time, nloc + 1, 0xff));
+    return 0;
+}
+
+// tracing (tracker counters, status records, the first-query log, the
+// profile), the hosts' own heartbeat intervals and the capture rings
+static int setup_tracing(TcpRun& r, const shd_tcp_model* m, const TcpPlan& p, int32_t trace) {
+    Glob& g = r.g;
+    const size_t nloc = (size_t)p.nloc;
     if (trace & SHD_TCP_TRACE_NODE) {   // every heartbeat before the end, per host
-        g.node_k = (uint32_t)((m->end_time - 1) / hb_min) + 1;
-        if (ws_alloc(ws, kWsNode, &g.node, sizeof(uint64_t) * 2 * kTrk * (size_t)nloc * g.node_k) != hipSuccess) {
-            (void)hipGetLastError();
-            fprintf(stderr, "shd_tcp_run: no device memory for the tracker counters\n");
-            rc = -12;
-            goto done;
-        }
+        g.node_k = (uint32_t)((m->end_time - 1) / p.hb_min) + 1;
+        WS_NEED(r.alloc(kWsNode, &g.node, 2 * kTrk * nloc * g.node_k), "shd_tcp_run: no device memory for the tracker counters\n");
     }
     if (g.trace) {
         // kTr records and kTrSack SACK words per host (about 16 MB): a traced
         // run of many hosts may not fit; say so instead of a bare -ENOMEM
-        const size_t need = (sizeof(TRec) * (size_t)kTr + sizeof(int32_t) * (size_t)kTrSack) * (size_t)nloc;
-        if (ws_alloc(ws, kWsTr, &g.tr, sizeof(TRec) * (size_t)nloc * kTr) != hipSuccess ||
-            ws_alloc(ws, kWsTrs, &g.trs, sizeof(int32_t) * (size_t)nloc * kTrSack) != hipSuccess) {
-            (void)hipGetLastError();
-            fprintf(stderr, "shd_tcp_run: no device memory for the status trace of %d hosts (%.1f GB); "
-                            "run without trace\n", nloc, need / 1e9);
-            rc = -12;
-            goto done;
-        }
+        const size_t need = (sizeof(TRec) * (size_t)kTr + sizeof(int32_t) * (size_t)kTrSack) * nloc;
+        WS_NEED(r.alloc(kWsTr, &g.tr, nloc * kTr) && r.alloc(kWsTrs, &g.trs, nloc * kTrSack),
+                "shd_tcp_run: no device memory for the status trace of %d hosts (%.1f GB); "
+                "run without trace\n", p.nloc, need / 1e9);
     }
     if (m->host_heartbeat) {
-        if (ws_alloc(ws, kWsHostHb, &d_hbh, sizeof(uint64_t) * (size_t)nloc) != hipSuccess) {
-            (void)hipGetLastError();
-            fprintf(stderr, "shd_tcp_run: no device memory for the hosts' heartbeat intervals\n");
-            rc = -12;
-            goto done;
-        }
-        HCHECK(hipMemcpy(d_hbh, m->host_heartbeat + h0, sizeof(uint64_t) * (size_t)nloc, hipMemcpyHostToDevice));
-        g.hb_host = d_hbh;
+        uint64_t* d_hb = nullptr;
+        WS_NEED(r.alloc(kWsHostHb, &d_hb, nloc), "shd_tcp_run: no device memory for the hosts' heartbeat intervals\n");
+        HCHECK(hipMemcpy(d_hb, m->host_heartbeat + p.h0, sizeof(uint64_t) * nloc, hipMemcpyHostToDevice));
+        g.hb_host = d_hb;
     }
-    if (any_pcap) {   // a ring per capture host of this engine, by capture slot: nothing per model host but the slot
+    if (p.any_pcap) {   // a ring per capture host of this engine, by capture slot: nothing per model host but the slot
+        TcpPcap& pcp = r.live.pcp;
         std::vector<int32_t> slot(nloc, -1);
-        for (int32_t i = 0; i < nloc; i++)
-            if (m->pcap_host[h0 + i]) {
+        for (int32_t i = 0; i < p.nloc; i++)
+            if (m->pcap_host[p.h0 + i]) {
                 slot[i] = (int32_t)pcp.host.size();
                 pcp.host.push_back(i);
             }
         const size_t ns = pcp.host.size();
         if (ns) {
+            int32_t* d_slot = nullptr;
             g.pcap_ring = m->pcap_ring ? m->pcap_ring : kPcapRing;
             const size_t need = sizeof(shd_pcap_rec) * ns * (size_t)g.pcap_ring;
-            if (ws_alloc(ws, kWsPcap, &g.pcrec, need) != hipSuccess ||
-                ws_alloc(ws, kWsNpcap, &g.npcap, sizeof(uint32_t) * ns) != hipSuccess ||
-                ws_alloc(ws, kWsPcapSlot, &d_pslot, sizeof(int32_t) * (size_t)nloc) != hipSuccess) {
-                (void)hipGetLastError();
-                fprintf(stderr, "shd_tcp_run: no device memory for the capture rings of %zu hosts (%.1f GB); "
-                                "capture fewer hosts or set a smaller pcap_ring\n", ns, need / 1e9);
-                rc = -12;
-                goto done;
-            }
+            WS_NEED(r.alloc(kWsPcap, &g.pcrec, ns * (size_t)g.pcap_ring) && r.alloc(kWsNpcap, &g.npcap, ns) &&
+                        r.alloc(kWsPcapSlot, &d_slot, nloc),
+                    "shd_tcp_run: no device memory for the capture rings of %zu hosts (%.1f GB); "
+                    "capture fewer hosts or set a smaller pcap_ring\n", ns, need / 1e9);
             HCHECK(hipMemset(g.npcap, 0, sizeof(uint32_t) * ns));
-            HCHECK(hipMemcpy(d_pslot, slot.data(), sizeof(int32_t) * (size_t)nloc, hipMemcpyHostToDevice));
-            g.pcap_slot = d_pslot;
+            HCHECK(hipMemcpy(d_slot, slot.data(), sizeof(int32_t) * nloc, hipMemcpyHostToDevice));
+            g.pcap_slot = d_slot;
             g.pcap_on = 1;
             pcp.cnt.assign(ns, 0);
             pcp.recs.resize(ns);
         }
     }
-    HCHECK(ws_alloc(ws, kWsNextTime, &g.next_time, sizeof(uint64_t) * (nloc + 1)));
-    HCHECK(hipMemset(g.next_time, 0xff, sizeof(uint64_t) * (nloc + 1)));
     // every host can log kPq first queries (touch_log)
-    g.qlog_cap = (uint32_t)nloc * kPq > (1u << 16) ? (uint32_t)nloc * kPq : (1u << 16);
-    HCHECK(ws_alloc(ws, kWsQlog, &g.qlog, sizeof(shd_tcp_query) * (size_t)g.qlog_cap));
-    HCHECK(ws_alloc(ws, kWsNqlog, &g.nqlog, sizeof(uint32_t)));
+    g.qlog_cap = (uint32_t)p.nloc * kPq > (1u << 16) ? (uint32_t)p.nloc * kPq : (1u << 16);
+    HCHECK(ws_alloc(r.ws, kWsQlog, &g.qlog, sizeof(shd_tcp_query) * (size_t)g.qlog_cap));
+    TRY(r.zero(kWsNqlog, &g.nqlog, 1));
 #ifdef SHD_TCP_PROF
-    HCHECK(ws_alloc(ws, kWsProf, &g.prof, sizeof(uint64_t) * 2 * kProf * (size_t)nloc));
-    HCHECK(hipMemset(g.prof, 0, sizeof(uint64_t) * 2 * kProf * (size_t)nloc));
-    HCHECK(ws_alloc(ws, kWsProfRound, &g.prof_round, sizeof(uint32_t) * 2 * kProfRounds));
-    HCHECK(hipMemset(g.prof_round, 0, sizeof(uint32_t) * 2 * kProfRounds));
+    TRY(r.zero(kWsProf, &g.prof, 2 * kProf * nloc));
+    TRY(r.zero(kWsProfRound, &g.prof_round, 2 * kProfRounds));
 #endif
-    HCHECK(hipMemset(g.nqlog, 0, sizeof(uint32_t)));
-    HCHECK(hipEventCreate(&e0));
-    HCHECK(hipEventCreate(&e1));
-    HCHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    // the initialisation above (k_tcp_free_init, the memsets) ran on the null
-    // stream, which a non-blocking stream does not wait for: finish it first
+    return 0;
+}
+
+// the run's stream and events.  The initialisation above (k_tcp_free_init,
+// the memsets) ran on the null stream, which a non-blocking stream does not
+// wait for: finish it before the stream's first use
+static int setup_stream(TcpRun& r) {
+    HCHECK(hipEventCreate(&r.e0));
+    HCHECK(hipEventCreate(&r.e1));
+    HCHECK(hipStreamCreateWithFlags(&r.st, hipStreamNonBlocking));
     HCHECK(hipDeviceSynchronize());
-    res->setup_ms = ms_since(t_call);
-    {
-        // rounds run in batches of kBatch (window kernel, round kernel) pairs
-        // captured once as a graph: no host round trip inside a batch; a
-        // halted run turns the batch's remaining kernels into no-ops
-        // one host per lane, 64 per wave (16 per wave measured +4 % at 16 k
-        // hosts, DESIGN.md §6: not kept)
-        const int threads = 64, blocks = (nloc + threads - 1) / threads;
-        constexpr int kBatch = 64;
-        if (world == 1) {
-            HCHECK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-            for (int i = 0; i < kBatch; i++) {
-                k_tcp_window<<<1, 1024, 0, st>>>(g, 0);
-                k_tcp_round<<<blocks, threads, 0, st>>>(g);
-            }
-            HCHECK(hipStreamEndCapture(st, &graph));
-            HCHECK(hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0));
-        }
-        HCHECK(hipEventRecord(e0, st));
-        k_tcp_boot<<<blocks, threads, 0, st>>>(g);
-        HCHECK(hipGetLastError());
-        for (;;) {
-            if (world == 1) {
-                HCHECK(hipGraphLaunch(gexec, st));
-                HCHECK(hipMemcpyAsync(&hctl, g.ctl, sizeof(TCtl), hipMemcpyDeviceToHost, st));
-                if (g.pcap_on)   // the batch's captures: the counts with the control word, then the rings' used parts
-                    HCHECK(hipMemcpyAsync(pcp.cnt.data(), g.npcap, sizeof(uint32_t) * pcp.cnt.size(),
-                                          hipMemcpyDeviceToHost, st));
-                if (g.ser_on)    // the batch's samples: the counter with the control word, then the array's used part
-                    HCHECK(hipMemcpyAsync(&ser.cnt, g.nser, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-                HCHECK(hipStreamSynchronize(st));
-                if (g.pcap_on) HCHECK(pcap_drain(pcp, g, st));
-                if (g.ser_on) HCHECK(series_drain(ser, g, st));
-            } else {
-                // a group's round (slave.c:437-462 across engines): the earliest
-                // event over the group opens the window; the round's ports and
-                // deliveries for the other engines are exchanged after it
-                k_tcp_window<<<1, 1024, 0, st>>>(g, 1);
-                k_tcp_ports_pack<<<1, 256, 0, st>>>(g, d_pmine);
-                HCHECK(hipMemcpyAsync(&hctl, g.ctl, sizeof(TCtl), hipMemcpyDeviceToHost, st));
-                HCHECK(hipStreamSynchronize(st));
-                struct { uint64_t tmin; uint32_t nport, halted; } mine{hctl.tmin, 0, hctl.halted}, all[64];
-                {
-                    uint64_t np = 0;
-                    HCHECK(hipMemcpy(&np, d_pmine, sizeof(uint64_t), hipMemcpyDeviceToHost));
-                    mine.nport = (uint32_t)np;
-                }
-                static_assert(sizeof(mine) <= 1024, "control word");
-                if (group_allgather(comm, d_gmine, d_gall, &mine, all, sizeof(mine), st)) { rc = -5; goto done; }
-                uint64_t t = ~0ull;
-                uint32_t anyport = 0, halted = 0;
-                for (int r = 0; r < world; r++) {
-                    t = all[r].tmin < t ? all[r].tmin : t;
-                    anyport |= all[r].nport;
-                    halted |= all[r].halted;
-                }
-                if (anyport) {
-                    if (shd_comm_allgather_dev(comm, d_pmine, d_pall, sizeof(uint64_t) * (1 + g.pcap), st)) {
-                        rc = -5;
-                        goto done;
-                    }
-                    k_tcp_ports<<<world, 256, 0, st>>>(g, d_pall);
-                }
-                if (halted) t = ~0ull;   // an engine stopped: every engine ends at the same round
-                k_tcp_decide<<<1, 64, 0, st>>>(g, t);
-                if (t == ~0ull || t >= g.end_time) {
-                    HCHECK(hipMemcpyAsync(&hctl, g.ctl, sizeof(TCtl), hipMemcpyDeviceToHost, st));
-                    HCHECK(hipStreamSynchronize(st));
-                    break;
-                }
-                k_tcp_round<<<blocks, threads, 0, st>>>(g);
-                HCHECK(hipGetLastError());
-                {   // the segments' used parts only: the counts first (one all-gather), then an all-to-all-v
-                    uint32_t heads[129], allh[64 * 129];
-                    const size_t hs = 2 * (size_t)world + 1;   // per engine: its segments' counts, its log entries
-                    k_tcp_xheads<<<1, 64, 0, st>>>(g, d_xcnt);
-                    HCHECK(hipMemcpyAsync(heads, d_xcnt, sizeof(uint32_t) * hs, hipMemcpyDeviceToHost, st));
-                    HCHECK(hipStreamSynchronize(st));
-                    if (group_allgather(comm, d_gmine, d_gall, heads, allh, sizeof(uint32_t) * hs, st)) {
-                        rc = -5;
-                        goto done;
-                    }
-                    if (g.pcm) {   // the round's first touches: every engine's log replayed alike (k_tcp_window)
-                        uint32_t mx = 0, tot = 0;
-                        for (int r = 0; r < world; r++) {
-                            const uint32_t n = allh[(size_t)r * hs + 2 * world];
-                            mx = n > mx ? n : mx;
-                            tot += n;
-                        }
-                        if (mx) {
-                            if (mx > g.ft_cap || tot > g.ft_cap) { res->error |= SHD_TCP_ERR_FIRST_TOUCH; break; }
-                            std::vector<shd_tcp_query> mine_q(mx), all_q((size_t)mx * world);
-                            const uint32_t nme = allh[(size_t)me * hs + 2 * world];
-                            if (nme) HCHECK(hipMemcpy(mine_q.data(), g.ft, sizeof(shd_tcp_query) * nme, hipMemcpyDeviceToHost));
-                            if (shd_comm_allgather_host(comm, mine_q.data(), sizeof(shd_tcp_query) * mx, all_q.data())) {
-                                rc = -5;
-                                goto done;
-                            }
-                            std::vector<shd_tcp_query> uni;
-                            uni.reserve(tot);
-                            for (int r = 0; r < world; r++)
-                                for (uint32_t j = 0; j < allh[(size_t)r * hs + 2 * world]; j++)
-                                    uni.push_back(all_q[(size_t)r * mx + j]);
-                            HCHECK(hipMemcpy(g.ft, uni.data(), sizeof(shd_tcp_query) * tot, hipMemcpyHostToDevice));
-                            HCHECK(hipMemcpy(g.nft, &tot, sizeof(uint32_t), hipMemcpyHostToDevice));
-                        }
-                    }
-                    size_t so[64], sb[64], ro[64], rb[64], so2[64], sb2[64], ro2[64], rb2[64];
-                    uint32_t mine_in[128];
-                    const size_t sack_at = sizeof(XSegHead) + (size_t)g.xcap * sizeof(Mail);
-                    for (int p = 0; p < world; p++) {
-                        const bool self = p == me;
-                        so[p] = ro[p] = (size_t)p * g.xseg + sizeof(XSegHead);
-                        so2[p] = ro2[p] = (size_t)p * g.xseg + sack_at;
-                        sb[p] = self ? 0 : (size_t)heads[2 * p] * sizeof(Mail);
-                        sb2[p] = self ? 0 : (size_t)heads[2 * p + 1] * sizeof(int32_t);
-                        const uint32_t* from = allh + (size_t)p * hs + 2 * me;   // what p sent this engine
-                        mine_in[2 * p] = self ? 0 : from[0];
-                        mine_in[2 * p + 1] = self ? 0 : from[1];
-                        rb[p] = (size_t)mine_in[2 * p] * sizeof(Mail);
-                        rb2[p] = (size_t)mine_in[2 * p + 1] * sizeof(int32_t);
-                    }
-                    if (shd_comm_alltoallv_dev(comm, g.xsend, so, sb, d_xrecv, ro, rb, st) ||
-                        shd_comm_alltoallv_dev(comm, g.xsend, so2, sb2, d_xrecv, ro2, rb2, st)) {
-                        rc = -5;
-                        goto done;
-                    }
-                    // (blocking: the counts leave this stack frame; the last round's ingest has finished)
-                    HCHECK(hipMemcpy(d_xcnt + hs, mine_in, sizeof(uint32_t) * 2 * world, hipMemcpyHostToDevice));
-                    k_tcp_xingest<<<world, 256, 0, st>>>(g, d_xrecv, d_xcnt + hs);
-                }
-                HCHECK(hipGetLastError());
-                HCHECK(hipMemcpyAsync(&hctl, g.ctl, sizeof(TCtl), hipMemcpyDeviceToHost, st));
-                if (g.pcap_on)
-                    HCHECK(hipMemcpyAsync(pcp.cnt.data(), g.npcap, sizeof(uint32_t) * pcp.cnt.size(),
-                                          hipMemcpyDeviceToHost, st));
-                if (g.ser_on) HCHECK(hipMemcpyAsync(&ser.cnt, g.nser, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-                HCHECK(hipStreamSynchronize(st));
-                if (g.pcap_on) {   // a drain every 64 rounds at the latest, or once a ring is past half
-                    bool due = ++pcp.rounds_since >= 64;
-                    for (uint32_t n : pcp.cnt) due |= n > g.pcap_ring / 2;
-                    if (due) HCHECK(pcap_drain(pcp, g, st));
-                }
-                if (g.ser_on && (++ser.rounds_since >= 64 || ser.cnt > g.ser_cap / 2))   // the sample array alike
-                    HCHECK(series_drain(ser, g, st));
-            }
-            if (hctl.halted) break;
-            if (hctl.rounds > (1ull << 26)) { res->error |= SHD_TCP_ERR_INTERNAL; break; }
-        }
-        rounds = hctl.rounds;
-        if (g.pcap_on) {   // what the rings hold since the last drain (a group's last rounds)
-            HCHECK(hipMemcpyAsync(pcp.cnt.data(), g.npcap, sizeof(uint32_t) * pcp.cnt.size(), hipMemcpyDeviceToHost, st));
-            HCHECK(hipStreamSynchronize(st));
-            HCHECK(pcap_drain(pcp, g, st));
-        }
-        if (g.ser_on) {   // the records still touched (k_tcp_series_flush), with what the array holds since the last drain
-            k_tcp_series_flush<<<(unsigned)((nloc + 255) / 256), 256, 0, st>>>(g);
-            HCHECK(hipGetLastError());
-            HCHECK(hipMemcpyAsync(&ser.cnt, g.nser, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            HCHECK(hipStreamSynchronize(st));
-            HCHECK(series_drain(ser, g, st));
-        }
-        HCHECK(hipEventRecord(e1, st));
-        HCHECK(hipEventSynchronize(e1));
-        float ms = 0;
-        HCHECK(hipEventElapsedTime(&ms, e0, e1));
-        res->device_ms = ms;
+    return 0;
+}
+
+static int tcp_setup(TcpRun& r, const shd_tcp_model* m, const TcpPlan& p, int32_t trace, const TcpSched* sch) {
+    TRY(setup_model(r, m, p, trace));
+    if (p.any_udp) TRY(setup_datagram_app(r, m));
+    TRY(setup_paths(r, m, p, sch));
+    if (p.world > 1) TRY(setup_exchange(r));
+    TRY(setup_hosts(r, m, p));
+    TRY(setup_options(r, m, p));
+    TRY(setup_packets(r));
+    TRY(setup_tracing(r, m, p, trace));
+    return setup_stream(r);
+}
+
+// Phase 3, the rounds.  Glob is read-only from here on (the launches copy it by value).
+
+// the capture rings' fill counts / the series' append counter to the host,
+// behind what the stream holds (the caller waits for the stream)
+static int pcap_counts_back(const TcpRun& r, TcpPcap& pcp) {
+    if (!r.g.pcap_on) return 0;
+    HCHECK(hipMemcpyAsync(pcp.cnt.data(), r.g.npcap, sizeof(uint32_t) * pcp.cnt.size(), hipMemcpyDeviceToHost, r.st));
+    return 0;
+}
+static int series_count_back(const TcpRun& r, TcpSeries& ser) {
+    if (!r.g.ser_on) return 0;
+    HCHECK(hipMemcpyAsync(&ser.cnt, r.g.nser, sizeof(uint32_t), hipMemcpyDeviceToHost, r.st));
+    return 0;
+}
+// the drain of the counts just copied, if it is due: always (`now`: a batch's
+// or the run's end), else every 64 rounds at the latest or once a ring / the
+// sample array is past half
+static int pcap_drain_due(const TcpRun& r, TcpPcap& pcp, bool now) {
+    if (!r.g.pcap_on) return 0;
+    bool due = now || ++pcp.rounds_since >= 64;
+    for (uint32_t n : pcp.cnt) due |= n > r.g.pcap_ring / 2;
+    if (due) HCHECK(pcap_drain(pcp, r.g, r.st));
+    return 0;
+}
+static int series_drain_due(const TcpRun& r, TcpSeries& ser, bool now) {
+    if (!r.g.ser_on) return 0;
+    if (now || ++ser.rounds_since >= 64 || ser.cnt > r.g.ser_cap / 2) HCHECK(series_drain(ser, r.g, r.st));
+    return 0;
+}
+// the control word and the counters after a batch or a round, then the drains
+static int round_end(const TcpRun& r, TcpLive& lv, bool drain_now) {
+    HCHECK(hipMemcpyAsync(&lv.hctl, r.g.ctl, sizeof(TCtl), hipMemcpyDeviceToHost, r.st));
+    TRY(pcap_counts_back(r, lv.pcp));
+    TRY(series_count_back(r, lv.ser));
+    HCHECK(hipStreamSynchronize(r.st));
+    TRY(pcap_drain_due(r, lv.pcp, drain_now));
+    return series_drain_due(r, lv.ser, drain_now);
+}
+
+// One engine: rounds run in batches of kBatch (window kernel, round kernel)
+// pairs captured once as a graph: no host round trip inside a batch; a
+// halted run turns the batch's remaining kernels into no-ops.  After each
+// batch one copy back, then the batch's captures and samples.
+static int rounds_capture(TcpRun& r) {
+    constexpr int kBatch = 64;
+    const Glob& g = r.g;
+    HCHECK(hipStreamBeginCapture(r.st, hipStreamCaptureModeThreadLocal));
+    for (int i = 0; i < kBatch; i++) {
+        k_tcp_window<<<1, 1024, 0, r.st>>>(g, 0);
+        k_tcp_round<<<lane_blocks(g), kLaneThreads, 0, r.st>>>(g);
     }
-    t_results = std::chrono::steady_clock::now();
-    HCHECK(hipMemcpy(hout.data(), g.host, sizeof(DHost) * nloc, hipMemcpyDeviceToHost));
-    {   // the first-query log (a group's: every engine's, so that each ranks the run's first touches alike)
-        uint32_t nq = 0;
-        HCHECK(hipMemcpy(&nq, g.nqlog, sizeof(uint32_t), hipMemcpyDeviceToHost));
-        if (nq > g.qlog_cap) nq = g.qlog_cap;   // (the run's error bits say so)
-        std::vector<shd_tcp_query> mine(nq ? nq : 1);
-        if (nq) HCHECK(hipMemcpy(mine.data(), g.qlog, sizeof(shd_tcp_query) * nq, hipMemcpyDeviceToHost));
-        if (world == 1) {
-            res->queries = (shd_tcp_query*)malloc(sizeof(shd_tcp_query) * (nq ? nq : 1));
-            memcpy(res->queries, mine.data(), sizeof(shd_tcp_query) * (nq ? nq : 1));
-            res->n_queries = nq;
-        } else {
-            std::vector<uint32_t> counts(world);
-            if (shd_comm_allgather_host(comm, &nq, sizeof(nq), counts.data())) { rc = -5; goto done; }
-            uint32_t mx = 1, tot = 0;
-            for (uint32_t c : counts) { mx = c > mx ? c : mx; tot += c; }
-            mine.resize(mx);
-            std::vector<shd_tcp_query> all((size_t)mx * world);
-            if (shd_comm_allgather_host(comm, mine.data(), sizeof(shd_tcp_query) * mx, all.data())) { rc = -5; goto done; }
-            res->queries = (shd_tcp_query*)malloc(sizeof(shd_tcp_query) * (tot ? tot : 1));
-            res->n_queries = tot;
-            size_t o = 0;
-            for (int r = 0; r < world; r++)
-                for (uint32_t j = 0; j < counts[r]; j++) res->queries[o++] = all[(size_t)r * mx + j];
-        }
+    HCHECK(hipStreamEndCapture(r.st, &r.graph));
+    HCHECK(hipGraphInstantiate(&r.gexec, r.graph, nullptr, nullptr, 0));
+    return 0;
+}
+static int rounds_one_engine(const TcpRun& r, TcpLive& lv, shd_tcp_result* res) {
+    for (;;) {
+        HCHECK(hipGraphLaunch(r.gexec, r.st));
+        TRY(round_end(r, lv, true));
+        if (lv.hctl.halted) return 0;
+        if (lv.hctl.rounds > (1ull << 26)) { res->error |= SHD_TCP_ERR_INTERNAL; return 0; }
     }
-    res->first_host = h0;
-    res->n_local_hosts = nloc;
-    res->next_event_id = (uint64_t*)calloc(nloc, sizeof(uint64_t));
-    res->next_packet_id = (uint64_t*)calloc(nloc, sizeof(uint64_t));
-    res->rng_probe = (uint32_t*)calloc(nloc, sizeof(uint32_t));
-    res->rounds = rounds;
-    if (g.flow_on) {   // the records, compacted on the device in the result's order (k_tcp_flow_*)
-        const int32_t ns = so[nloc];
-        uint32_t nf = 0;
-        shd_tcp_flow* d_out = nullptr;
-        HCHECK(hipEventRecord(e0, st));
-        k_tcp_flow_count<<<(unsigned)((nloc + 255) / 256), 256, 0, st>>>(g, d_fcnt);
-        k_tcp_flow_scan<<<1, kFlowScan, 0, st>>>(d_fcnt, d_foff, nloc);
-        HCHECK(hipGetLastError());
-        HCHECK(hipMemcpyAsync(&nf, d_foff + nloc, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        HCHECK(hipStreamSynchronize(st));
-        if (nf > (uint32_t)ns) { rc = -5; goto done; }   // (more records than slots: never)
-        resx->flows = (shd_tcp_flow*)malloc(sizeof(shd_tcp_flow) * (nf ? nf : 1));
-        resx->n_flows = nf;
-        if (nf) {
-            HCHECK(ws_alloc(ws, kWsFlowOut, &d_out, sizeof(shd_tcp_flow) * nf));
-            k_tcp_flow_write<<<(unsigned)((ns + 255) / 256), 256, 0, st>>>(g, d_foff, d_out, ns, d_smap);
-            HCHECK(hipGetLastError());
-            HCHECK(hipMemcpyAsync(resx->flows, d_out, sizeof(shd_tcp_flow) * nf, hipMemcpyDeviceToHost, st));
-        }
-        HCHECK(hipEventRecord(e1, st));
-        HCHECK(hipEventSynchronize(e1));
-        if (getenv("SHD_TCP_FLOW_TIMING")) {   // the gather's device time (kernels and the copy back), for measurements
-            float fms = 0;
-            HCHECK(hipEventElapsedTime(&fms, e0, e1));
-            fprintf(stderr, "shd_tcp_run: %u flow records of %d slots gathered in %.3f ms\n", nf, ns, fms);
-        }
-        if (g.ser_on) {   // the samples name their record (the gather's slot map) and come sorted by (flow, t)
-            const size_t n = ser.recs.size();
-            resx->series_info.drains = ser.drains;
-            resx->series_info.peak = ser.peak;
-            resx->series_info.capacity = g.ser_cap;
-            resx->series = (shd_tcp_sample*)malloc(sizeof(shd_tcp_sample) * (n ? n : 1));
-            if (!resx->series) { rc = -12; goto done; }
-            if (n) {
-                std::vector<uint32_t> smap((size_t)ns);
-                HCHECK(hipMemcpy(smap.data(), d_smap, sizeof(uint32_t) * (size_t)ns, hipMemcpyDeviceToHost));
-                for (shd_tcp_sample& r : ser.recs) {
-                    if (r.flow >= (uint32_t)ns || smap[r.flow] >= nf) { rc = -5; goto done; }   // (a sample of no record: never)
-                    r.flow = smap[r.flow];
-                }
-                std::sort(ser.recs.begin(), ser.recs.end(), [](const shd_tcp_sample& a, const shd_tcp_sample& b) {
-                    return a.flow != b.flow ? a.flow < b.flow : a.t < b.t;
-                });
-                memcpy(resx->series, ser.recs.data(), sizeof(shd_tcp_sample) * n);
-            }
-            resx->n_series = n;
-            if (getenv("SHD_TCP_SERIES_TIMING"))   // the drains' host wall time (copies and their waits), for measurements
-                fprintf(stderr, "shd_tcp_run: %zu samples in %llu drains (peak %u of %u), drains %.3f ms\n", n,
-                        (unsigned long long)ser.drains, ser.peak, g.ser_cap, ser.drain_ms);
-        }
+}
+
+// A group's round (slave.c:437-462 across engines): the earliest event over
+// the group opens the window; the round's ports and deliveries for the other
+// engines are exchanged after it.  Every rank issues the same collectives in
+// the same order: what decides a step is all-gathered first.
+
+// agree on the window and the ports: *t the round's start over the group, ~0 to end the run
+static int group_agree(const TcpRun& r, shd_comm* comm, TcpLive& lv, uint64_t* t) {
+    const Glob& g = r.g;
+    k_tcp_window<<<1, 1024, 0, r.st>>>(g, 1);
+    k_tcp_ports_pack<<<1, 256, 0, r.st>>>(g, r.xch.pmine);
+    HCHECK(hipMemcpyAsync(&lv.hctl, g.ctl, sizeof(TCtl), hipMemcpyDeviceToHost, r.st));
+    HCHECK(hipStreamSynchronize(r.st));
+    struct { uint64_t tmin; uint32_t nport, halted; } mine{lv.hctl.tmin, 0, lv.hctl.halted}, all[64];
+    uint64_t np = 0;
+    HCHECK(hipMemcpy(&np, r.xch.pmine, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    mine.nport = (uint32_t)np;
+    static_assert(sizeof(mine) <= kGatherMax, "control word");
+    if (group_allgather(comm, r.xch.gmine, r.xch.gall, &mine, all, sizeof(mine), r.st)) return -5;
+    *t = ~0ull;
+    uint32_t anyport = 0, halted = 0;
+    for (int w = 0; w < g.world; w++) {
+        *t = all[w].tmin < *t ? all[w].tmin : *t;
+        anyport |= all[w].nport;
+        halted |= all[w].halted;
     }
-    if (g.path_on) {   // the accumulators folded, the table compacted (k_tcp_path_*), the records named and sorted
-        const int32_t ns = so[nloc];
-        uint32_t np = 0, full = 0;
-        shd_tcp_path* d_out = nullptr;
-        HCHECK(hipEventRecord(e0, st));
-        if (ns) k_tcp_path_fold<<<(unsigned)((ns + 255) / 256), 256, 0, st>>>(g, ns);
-        k_tcp_path_count<<<(pt_cap + 255) / 256, 256, 0, st>>>(g.ptab, d_pcnt, pt_cap);
-        k_tcp_flow_scan<<<1, kFlowScan, 0, st>>>(d_pcnt, d_poff, (int32_t)pt_cap);
+    if (anyport) {
+        if (shd_comm_allgather_dev(comm, r.xch.pmine, r.xch.pall, sizeof(uint64_t) * (1 + g.pcap), r.st)) return -5;
+        k_tcp_ports<<<g.world, 256, 0, r.st>>>(g, r.xch.pall);
+    }
+    if (halted) *t = ~0ull;   // an engine stopped: every engine ends at the same round
+    k_tcp_decide<<<1, 64, 0, r.st>>>(g, *t);
+    return 0;
+}
+
+// merge the first-touch logs: the round's first touches, every engine's log
+// replayed alike (k_tcp_window).  allh: per engine hs words, the last its log's
+// entries.  *full: the logs do not fit (decided alike on every rank)
+static int group_merge_first_touch(const TcpRun& r, shd_comm* comm, const uint32_t* allh, size_t hs, bool* full) {
+    const Glob& g = r.g;
+    const int world = g.world;
+    uint32_t mx = 0, tot = 0;
+    for (int w = 0; w < world; w++) {
+        const uint32_t n = allh[(size_t)w * hs + 2 * world];
+        mx = n > mx ? n : mx;
+        tot += n;
+    }
+    *full = mx > g.ft_cap || tot > g.ft_cap;
+    if (!mx || *full) return 0;
+    std::vector<shd_tcp_query> mine_q(mx), all_q((size_t)mx * world);
+    const uint32_t nme = allh[(size_t)g.me * hs + 2 * world];
+    if (nme) HCHECK(hipMemcpy(mine_q.data(), g.ft, sizeof(shd_tcp_query) * nme, hipMemcpyDeviceToHost));
+    if (shd_comm_allgather_host(comm, mine_q.data(), sizeof(shd_tcp_query) * mx, all_q.data())) return -5;
+    std::vector<shd_tcp_query> uni;
+    uni.reserve(tot);
+    for (int w = 0; w < world; w++)
+        for (uint32_t j = 0; j < allh[(size_t)w * hs + 2 * world]; j++) uni.push_back(all_q[(size_t)w * mx + j]);
+    HCHECK(hipMemcpy(g.ft, uni.data(), sizeof(shd_tcp_query) * tot, hipMemcpyHostToDevice));
+    HCHECK(hipMemcpy(g.nft, &tot, sizeof(uint32_t), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// exchange the segments and ingest: the used parts only (heads: this engine's
+// counts, allh: every engine's), mails and SACK words in one all-to-all-v each
+static int group_exchange(const TcpRun& r, shd_comm* comm, const uint32_t* heads, const uint32_t* allh, size_t hs) {
+    const Glob& g = r.g;
+    const int world = g.world, me = g.me;
+    size_t so[64], sb[64], ro[64], rb[64], so2[64], sb2[64], ro2[64], rb2[64];
+    uint32_t mine_in[128];
+    const size_t sack_at = sizeof(XSegHead) + (size_t)g.xcap * sizeof(Mail);
+    for (int p = 0; p < world; p++) {
+        const bool self = p == me;
+        so[p] = ro[p] = (size_t)p * g.xseg + sizeof(XSegHead);
+        so2[p] = ro2[p] = (size_t)p * g.xseg + sack_at;
+        sb[p] = self ? 0 : (size_t)heads[2 * p] * sizeof(Mail);
+        sb2[p] = self ? 0 : (size_t)heads[2 * p + 1] * sizeof(int32_t);
+        const uint32_t* from = allh + (size_t)p * hs + 2 * me;   // what p sent this engine
+        mine_in[2 * p] = self ? 0 : from[0];
+        mine_in[2 * p + 1] = self ? 0 : from[1];
+        rb[p] = (size_t)mine_in[2 * p] * sizeof(Mail);
+        rb2[p] = (size_t)mine_in[2 * p + 1] * sizeof(int32_t);
+    }
+    if (shd_comm_alltoallv_dev(comm, g.xsend, so, sb, r.xch.recv, ro, rb, r.st) ||
+        shd_comm_alltoallv_dev(comm, g.xsend, so2, sb2, r.xch.recv, ro2, rb2, r.st))
+        return -5;
+    // (blocking: the counts leave this stack frame; the last round's ingest has finished)
+    HCHECK(hipMemcpy(r.xch.cnt + hs, mine_in, sizeof(uint32_t) * 2 * world, hipMemcpyHostToDevice));
+    k_tcp_xingest<<<world, 256, 0, r.st>>>(g, r.xch.recv, r.xch.cnt + hs);
+    return 0;
+}
+
+static int rounds_group(const TcpRun& r, shd_comm* comm, TcpLive& lv, shd_tcp_result* res) {
+    const Glob& g = r.g;
+    const size_t hs = 2 * (size_t)g.world + 1;   // per engine: its segments' counts, its log entries
+    for (;;) {
+        uint64_t t = ~0ull;
+        TRY(group_agree(r, comm, lv, &t));
+        if (t == ~0ull || t >= g.end_time) {
+            HCHECK(hipMemcpyAsync(&lv.hctl, g.ctl, sizeof(TCtl), hipMemcpyDeviceToHost, r.st));
+            HCHECK(hipStreamSynchronize(r.st));
+            return 0;
+        }
+        k_tcp_round<<<lane_blocks(g), kLaneThreads, 0, r.st>>>(g);
         HCHECK(hipGetLastError());
-        HCHECK(hipMemcpyAsync(&np, d_poff + pt_cap, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        HCHECK(hipMemcpyAsync(&full, g.pt_full, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        HCHECK(hipStreamSynchronize(st));
-        if (np > pt_cap) { rc = -5; goto done; }   // (more records than entries: never)
-        if (full) res->error |= SHD_TCP_ERR_PATHS;
-        resx->paths = (shd_tcp_path*)malloc(sizeof(shd_tcp_path) * (np ? np : 1));
-        if (!resx->paths) { rc = -12; goto done; }
-        resx->n_paths = np;
-        if (np) {
-            HCHECK(ws_alloc(ws, kWsPtOut, &d_out, sizeof(shd_tcp_path) * np));
-            k_tcp_path_write<<<(pt_cap + 255) / 256, 256, 0, st>>>(g.ptab, d_poff, d_out, pt_cap);
-            HCHECK(hipGetLastError());
-            HCHECK(hipMemcpyAsync(resx->paths, d_out, sizeof(shd_tcp_path) * np, hipMemcpyDeviceToHost, st));
+        // the segments' counts first (one all-gather), then the logs and the segments
+        uint32_t heads[129], allh[64 * 129];
+        k_tcp_xheads<<<1, 64, 0, r.st>>>(g, r.xch.cnt);
+        HCHECK(hipMemcpyAsync(heads, r.xch.cnt, sizeof(uint32_t) * hs, hipMemcpyDeviceToHost, r.st));
+        HCHECK(hipStreamSynchronize(r.st));
+        if (group_allgather(comm, r.xch.gmine, r.xch.gall, heads, allh, sizeof(uint32_t) * hs, r.st)) return -5;
+        if (g.pcm) {
+            bool full = false;
+            TRY(group_merge_first_touch(r, comm, allh, hs, &full));
+            if (full) { res->error |= SHD_TCP_ERR_FIRST_TOUCH; return 0; }
         }
-        HCHECK(hipEventRecord(e1, st));
-        HCHECK(hipEventSynchronize(e1));
-        if (getenv("SHD_TCP_PATH_TIMING")) {   // the fold's and gather's device time (with the copy back), for measurements
-            float pms = 0;
-            HCHECK(hipEventElapsedTime(&pms, e0, e1));
-            fprintf(stderr, "shd_tcp_run: %u path records from a table of %u entries (%d slots) folded and gathered in %.3f ms\n",
-                    np, pt_cap, ns, pms);
+        TRY(group_exchange(r, comm, heads, allh, hs));
+        HCHECK(hipGetLastError());
+        TRY(round_end(r, lv, false));
+        if (lv.hctl.halted) return 0;
+        if (lv.hctl.rounds > (1ull << 26)) { res->error |= SHD_TCP_ERR_INTERNAL; return 0; }
+    }
+}
+
+// the rounds from boot to the last drain; their device time
+static int tcp_rounds(TcpRun& r, shd_comm* comm, shd_tcp_result* res) {
+    const Glob& g = r.g;
+    TcpLive& lv = r.live;
+    if (g.world == 1) TRY(rounds_capture(r));
+    HCHECK(hipEventRecord(r.e0, r.st));
+    k_tcp_boot<<<lane_blocks(g), kLaneThreads, 0, r.st>>>(g);
+    HCHECK(hipGetLastError());
+    TRY(g.world == 1 ? rounds_one_engine(r, lv, res) : rounds_group(r, comm, lv, res));
+    // what the rings hold since the last drain (a group's last rounds)
+    TRY(pcap_counts_back(r, lv.pcp));
+    if (g.pcap_on) HCHECK(hipStreamSynchronize(r.st));
+    TRY(pcap_drain_due(r, lv.pcp, true));
+    if (g.ser_on) {   // the records still touched (k_tcp_series_flush), with what the array holds since the last drain
+        k_tcp_series_flush<<<(unsigned)((g.nloc + 255) / 256), 256, 0, r.st>>>(g);
+        HCHECK(hipGetLastError());
+        TRY(series_count_back(r, lv.ser));
+        HCHECK(hipStreamSynchronize(r.st));
+        TRY(series_drain_due(r, lv.ser, true));
+    }
+    HCHECK(hipEventRecord(r.e1, r.st));
+    HCHECK(hipEventSynchronize(r.e1));
+    float ms = 0;
+    HCHECK(hipEventElapsedTime(&ms, r.e0, r.e1));
+    res->device_ms = ms;
+    return 0;
+}
+
+// Phase 4, collect: the result, one part per function, in this order (tcp_collect).
+
+// the first-query log (a group's: every engine's, so that each ranks the run's first touches alike)
+static int collect_queries(const TcpRun& r, shd_comm* comm, shd_tcp_result* res) {
+    const Glob& g = r.g;
+    uint32_t nq = 0;
+    HCHECK(hipMemcpy(&nq, g.nqlog, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (nq > g.qlog_cap) nq = g.qlog_cap;   // (the run's error bits say so)
+    std::vector<shd_tcp_query> mine(nq ? nq : 1);
+    if (nq) HCHECK(hipMemcpy(mine.data(), g.qlog, sizeof(shd_tcp_query) * nq, hipMemcpyDeviceToHost));
+    if (g.world == 1) {
+        TRY(res_alloc(&res->queries, nq));
+        memcpy(res->queries, mine.data(), sizeof(shd_tcp_query) * (nq ? nq : 1));
+        res->n_queries = nq;
+        return 0;
+    }
+    std::vector<uint32_t> counts(g.world);
+    if (shd_comm_allgather_host(comm, &nq, sizeof(nq), counts.data())) return -5;
+    uint32_t mx = 1, tot = 0;
+    for (uint32_t c : counts) { mx = c > mx ? c : mx; tot += c; }
+    mine.resize(mx);
+    std::vector<shd_tcp_query> all((size_t)mx * g.world);
+    if (shd_comm_allgather_host(comm, mine.data(), sizeof(shd_tcp_query) * mx, all.data())) return -5;
+    TRY(res_alloc(&res->queries, tot));
+    res->n_queries = tot;
+    size_t o = 0;
+    for (int w = 0; w < g.world; w++)
+        for (uint32_t j = 0; j < counts[w]; j++) res->queries[o++] = all[(size_t)w * mx + j];
+    return 0;
+}
+
+// the samples under the flow records: they name their record (the gather's slot map) and come sorted by (flow, t)
+static int collect_series(const TcpRun& r, TcpSeries& ser, int32_t ns, uint32_t nf, TcpResultX* resx) {
+    const Glob& g = r.g;
+    const size_t n = ser.recs.size();
+    resx->series_info.drains = ser.drains;
+    resx->series_info.peak = ser.peak;
+    resx->series_info.capacity = g.ser_cap;
+    TRY(res_alloc(&resx->series, n));
+    if (n) {
+        std::vector<uint32_t> smap((size_t)ns);
+        HCHECK(hipMemcpy(smap.data(), r.series.map, sizeof(uint32_t) * (size_t)ns, hipMemcpyDeviceToHost));
+        for (shd_tcp_sample& s : ser.recs) {
+            if (s.flow >= (uint32_t)ns || smap[s.flow] >= nf) return -5;   // (a sample of no record: never)
+            s.flow = smap[s.flow];
         }
-        // the device's indices are Glob::hv's: the model's host_vertex on
-        // tables, the cache's attached indices otherwise -- named here
-        std::vector<int32_t> name(V, -1);
-        for (int32_t a = 0; a < H; a++) name[hvi[a]] = m->host_vertex[a];
-        for (uint32_t i = 0; i < np; i++) {
-            shd_tcp_path& r = resx->paths[i];
-            if (r.v_src < 0 || r.v_src >= V || r.v_dst < 0 || r.v_dst >= V) { rc = -5; goto done; }
-            r.v_src = name[r.v_src]; r.v_dst = name[r.v_dst];
-        }
-        std::sort(resx->paths, resx->paths + np, [](const shd_tcp_path& a, const shd_tcp_path& b) {
-            return a.v_src != b.v_src ? a.v_src < b.v_src : a.v_dst < b.v_dst;
+        std::sort(ser.recs.begin(), ser.recs.end(), [](const shd_tcp_sample& a, const shd_tcp_sample& b) {
+            return a.flow != b.flow ? a.flow < b.flow : a.t < b.t;
         });
+        memcpy(resx->series, ser.recs.data(), sizeof(shd_tcp_sample) * n);
     }
-    if (any_pcap) {   // the capture hosts' records, hosts in index order (the slots' order)
-        res->pcap_off = (uint64_t*)calloc((size_t)nloc + 1, sizeof(uint64_t));
-        size_t tot = 0;
-        for (const auto& v : pcp.recs) tot += v.size();
-        res->pcap_records = (shd_pcap_rec*)malloc(sizeof(shd_pcap_rec) * (tot ? tot : 1));
-        size_t o = 0, s = 0;
-        for (int32_t i = 0; i < nloc; i++) {
-            res->pcap_off[i] = o;
-            if (s < pcp.host.size() && pcp.host[s] == i) {
-                if (!pcp.recs[s].empty())
-                    memcpy(res->pcap_records + o, pcp.recs[s].data(), sizeof(shd_pcap_rec) * pcp.recs[s].size());
-                o += pcp.recs[s++].size();
-            }
-        }
-        res->pcap_off[nloc] = o;
-        res->pcap_drains = pcp.drains;
-        res->pcap_ring_peak = pcp.peak;
+    resx->n_series = n;
+    if (getenv("SHD_TCP_SERIES_TIMING"))   // the drains' host wall time (copies and their waits), for measurements
+        fprintf(stderr, "shd_tcp_run: %zu samples in %llu drains (peak %u of %u), drains %.3f ms\n", n,
+                (unsigned long long)ser.drains, ser.peak, g.ser_cap, ser.drain_ms);
+    return 0;
+}
+
+// the flow records, compacted on the device in the result's order (k_tcp_flow_*), with the series under them
+static int collect_flows(const TcpRun& r, TcpSeries& ser, int32_t ns, TcpResultX* resx) {
+    const Glob& g = r.g;
+    uint32_t nf = 0;
+    shd_tcp_flow* d_out = nullptr;
+    HCHECK(hipEventRecord(r.e0, r.st));
+    k_tcp_flow_count<<<(unsigned)((g.nloc + 255) / 256), 256, 0, r.st>>>(g, r.flows.cnt);
+    k_tcp_flow_scan<<<1, kFlowScan, 0, r.st>>>(r.flows.cnt, r.flows.off, g.nloc);
+    HCHECK(hipGetLastError());
+    HCHECK(hipMemcpyAsync(&nf, r.flows.off + g.nloc, sizeof(uint32_t), hipMemcpyDeviceToHost, r.st));
+    HCHECK(hipStreamSynchronize(r.st));
+    if (nf > (uint32_t)ns) return -5;   // (more records than slots: never)
+    TRY(res_alloc(&resx->flows, nf));
+    resx->n_flows = nf;
+    if (nf) {
+        HCHECK(ws_alloc(r.ws, kWsFlowOut, &d_out, sizeof(shd_tcp_flow) * nf));
+        k_tcp_flow_write<<<(unsigned)((ns + 255) / 256), 256, 0, r.st>>>(g, r.flows.off, d_out, ns, r.series.map);
+        HCHECK(hipGetLastError());
+        HCHECK(hipMemcpyAsync(resx->flows, d_out, sizeof(shd_tcp_flow) * nf, hipMemcpyDeviceToHost, r.st));
     }
-    {   // the last two rounds' mailboxes were never counted by k_tcp_window
-        std::vector<uint32_t> nm(2 * (kMailSub + 1));
-        HCHECK(hipMemcpy(nm.data(), g.nmail, sizeof(uint32_t) * nm.size(), hipMemcpyDeviceToHost));
-        TCtl cx;
-        HCHECK(hipMemcpy(&cx, g.ctl, sizeof(TCtl), hipMemcpyDeviceToHost));
-        res->max_round_deliveries = cx.max_mail;
-        res->max_round_overflow = cx.max_ovf;
-        if (cx.ft_bad) res->error |= SHD_TCP_ERR_FIRST_TOUCH;
-        if (cx.ft_bad && sch && pc && world == 1 && sch->round.size() < kFtReruns) {
-            // the contradicted round's first touches in serial order: the
-            // ranks its replay assigned, [ft_nr0, next_rank)
-            std::vector<int32_t> rk(V), sk(V);
-            int32_t nr1 = 0;
-            HCHECK(hipMemcpy(rk.data(), g.rank, sizeof(int32_t) * (size_t)V, hipMemcpyDeviceToHost));
-            HCHECK(hipMemcpy(sk.data(), g.srank, sizeof(int32_t) * (size_t)V, hipMemcpyDeviceToHost));
-            HCHECK(hipMemcpy(&nr1, g.next_rank, sizeof(int32_t), hipMemcpyDeviceToHost));
-            const int32_t nr0 = (int32_t)cx.ft_nr0;
-            std::vector<int32_t> ord(nr1 > nr0 ? nr1 - nr0 : 0, INT32_MIN);
-            for (int32_t v = 0; v < V; v++) {
-                if (rk[v] != kNoRank && rk[v] >= nr0 && rk[v] < nr1) ord[rk[v] - nr0] = v;
-                if (sk[v] != kNoRank && sk[v] >= nr0 && sk[v] < nr1) ord[sk[v] - nr0] = ~v;
-            }
-            bool ok = !ord.empty();
-            for (int32_t x : ord) ok &= x != INT32_MIN;
-            if (ok) {
-                sch->round.push_back((uint32_t)cx.rounds);
-                sch->v.insert(sch->v.end(), ord.begin(), ord.end());
-                sch->off.push_back((uint32_t)sch->v.size());
-                sch->extended = true;
-            }
-        }
-        res->error |= cx.xerr;
-        if (pc && !cx.ft_bad) {   // the cache's ranks as the serial run leaves them
-            std::vector<int32_t> old_rank(pc->h_rank, pc->h_rank + V), old_self(pc->h_self_rank, pc->h_self_rank + V);
-            HCHECK(hipMemcpy(pc->h_rank, g.rank, sizeof(int32_t) * (size_t)V, hipMemcpyDeviceToHost));
-            HCHECK(hipMemcpy(pc->h_self_rank, g.srank, sizeof(int32_t) * (size_t)V, hipMemcpyDeviceToHost));
-            HCHECK(hipMemcpy(&pc->next_rank, g.next_rank, sizeof(int32_t), hipMemcpyDeviceToHost));
-            // and minimumPathLatency with the entries those rows stored
-            if (const int fr = shd_pc_fold_ranked(pc, old_rank.data(), old_self.data())) { rc = fr; goto done; }
-        }
-        for (int b = 0; b < 2; b++) {
-            uint64_t sum = 0;
-            for (uint32_t j = 0; j <= kMailSub; j++) {
-                const uint32_t cap = j < kMailSub ? g.mail_part : g.mail_cap - g.mail_part * kMailSub;
-                const uint32_t v = nm[b * (kMailSub + 1) + j];
-                sum += v < cap ? v : cap;
-                if (j == kMailSub && (v < cap ? v : cap) > res->max_round_overflow) res->max_round_overflow = v < cap ? v : cap;
-            }
-            if (sum > res->max_round_deliveries) res->max_round_deliveries = sum;
-        }
+    HCHECK(hipEventRecord(r.e1, r.st));
+    HCHECK(hipEventSynchronize(r.e1));
+    if (getenv("SHD_TCP_FLOW_TIMING")) {   // the gather's device time (kernels and the copy back), for measurements
+        float fms = 0;
+        HCHECK(hipEventElapsedTime(&fms, r.e0, r.e1));
+        fprintf(stderr, "shd_tcp_run: %u flow records of %d slots gathered in %.3f ms\n", nf, ns, fms);
     }
+    return g.ser_on ? collect_series(r, ser, ns, nf, resx) : 0;
+}
+
+// the path records: the accumulators folded, the table compacted (k_tcp_path_*), the records named and sorted
+static int collect_paths(const TcpRun& r, const shd_tcp_model* m, const TcpPlan& p, TcpResultX* resx) {
+    const Glob& g = r.g;
+    const int32_t ns = p.so[p.nloc], V = p.V;
+    const uint32_t cap = r.paths.cap;
+    uint32_t np = 0, full = 0;
+    shd_tcp_path* d_out = nullptr;
+    HCHECK(hipEventRecord(r.e0, r.st));
+    if (ns) k_tcp_path_fold<<<(unsigned)((ns + 255) / 256), 256, 0, r.st>>>(g, ns);
+    k_tcp_path_count<<<(cap + 255) / 256, 256, 0, r.st>>>(g.ptab, r.paths.cnt, cap);
+    k_tcp_flow_scan<<<1, kFlowScan, 0, r.st>>>(r.paths.cnt, r.paths.off, (int32_t)cap);
+    HCHECK(hipGetLastError());
+    HCHECK(hipMemcpyAsync(&np, r.paths.off + cap, sizeof(uint32_t), hipMemcpyDeviceToHost, r.st));
+    HCHECK(hipMemcpyAsync(&full, g.pt_full, sizeof(uint32_t), hipMemcpyDeviceToHost, r.st));
+    HCHECK(hipStreamSynchronize(r.st));
+    if (np > cap) return -5;   // (more records than entries: never)
+    if (full) resx->pub.error |= SHD_TCP_ERR_PATHS;
+    TRY(res_alloc(&resx->paths, np));
+    resx->n_paths = np;
+    if (np) {
+        HCHECK(ws_alloc(r.ws, kWsPtOut, &d_out, sizeof(shd_tcp_path) * np));
+        k_tcp_path_write<<<(cap + 255) / 256, 256, 0, r.st>>>(g.ptab, r.paths.off, d_out, cap);
+        HCHECK(hipGetLastError());
+        HCHECK(hipMemcpyAsync(resx->paths, d_out, sizeof(shd_tcp_path) * np, hipMemcpyDeviceToHost, r.st));
+    }
+    HCHECK(hipEventRecord(r.e1, r.st));
+    HCHECK(hipEventSynchronize(r.e1));
+    if (getenv("SHD_TCP_PATH_TIMING")) {   // the fold's and gather's device time (with the copy back), for measurements
+        float pms = 0;
+        HCHECK(hipEventElapsedTime(&pms, r.e0, r.e1));
+        fprintf(stderr, "shd_tcp_run: %u path records from a table of %u entries (%d slots) folded and gathered in %.3f ms\n",
+                np, cap, ns, pms);
+    }
+    // the device's indices are Glob::hv's: the model's host_vertex on
+    // tables, the cache's attached indices otherwise -- named here
+    std::vector<int32_t> name(V, -1);
+    for (int32_t a = 0; a < m->n_hosts; a++) name[p.hvi[a]] = m->host_vertex[a];
+    for (uint32_t i = 0; i < np; i++) {
+        shd_tcp_path& x = resx->paths[i];
+        if (x.v_src < 0 || x.v_src >= V || x.v_dst < 0 || x.v_dst >= V) return -5;
+        x.v_src = name[x.v_src]; x.v_dst = name[x.v_dst];
+    }
+    std::sort(resx->paths, resx->paths + np, [](const shd_tcp_path& a, const shd_tcp_path& b) {
+        return a.v_src != b.v_src ? a.v_src < b.v_src : a.v_dst < b.v_dst;
+    });
+    return 0;
+}
+
+// Path.packetCount (topology_incrementPathPacketCounter, worker.c:296): the
+// cache's own counter, keyed on the unordered attached pair as
+// shd_pc_count_packet keys it, takes each pair's sends.  A run that a rerun
+// follows ended with SHD_TCP_ERR_FIRST_TOUCH and folds nothing.
+static void collect_path_packets(shd_pc* pc, const TcpResultX* resx) {
+    for (uint64_t i = 0; i < resx->n_paths; i++) {
+        const shd_tcp_path& x = resx->paths[i];
+        if (x.packets_sent) shd_pc_add_packets(pc, pc->h_att_index[x.v_src], pc->h_att_index[x.v_dst], x.packets_sent);
+    }
+}
+
+// the capture hosts' records, hosts in index order (the slots' order)
+static int collect_pcap(const TcpPcap& pcp, int32_t nloc, shd_tcp_result* res) {
+    TRY(res_alloc(&res->pcap_off, (size_t)nloc + 1));
+    size_t tot = 0;
+    for (const auto& v : pcp.recs) tot += v.size();
+    TRY(res_alloc(&res->pcap_records, tot));
+    size_t o = 0, s = 0;
     for (int32_t i = 0; i < nloc; i++) {
+        res->pcap_off[i] = o;
+        if (s < pcp.host.size() && pcp.host[s] == i) {
+            if (!pcp.recs[s].empty())
+                memcpy(res->pcap_records + o, pcp.recs[s].data(), sizeof(shd_pcap_rec) * pcp.recs[s].size());
+            o += pcp.recs[s++].size();
+        }
+    }
+    res->pcap_off[nloc] = o;
+    res->pcap_drains = pcp.drains;
+    res->pcap_ring_peak = pcp.peak;
+    return 0;
+}
+
+// a contradicted round's first touches in serial order, for the call's next
+// run: the ranks that round's replay assigned, [ft_nr0, next_rank)
+static int sched_extend(const Glob& g, const TCtl& cx, int32_t V, TcpSched* sch) {
+    std::vector<int32_t> rk(V), sk(V);
+    int32_t nr1 = 0;
+    HCHECK(hipMemcpy(rk.data(), g.rank, sizeof(int32_t) * (size_t)V, hipMemcpyDeviceToHost));
+    HCHECK(hipMemcpy(sk.data(), g.srank, sizeof(int32_t) * (size_t)V, hipMemcpyDeviceToHost));
+    HCHECK(hipMemcpy(&nr1, g.next_rank, sizeof(int32_t), hipMemcpyDeviceToHost));
+    const int32_t nr0 = (int32_t)cx.ft_nr0;
+    std::vector<int32_t> ord(nr1 > nr0 ? nr1 - nr0 : 0, INT32_MIN);
+    for (int32_t v = 0; v < V; v++) {
+        if (rk[v] != kNoRank && rk[v] >= nr0 && rk[v] < nr1) ord[rk[v] - nr0] = v;
+        if (sk[v] != kNoRank && sk[v] >= nr0 && sk[v] < nr1) ord[sk[v] - nr0] = ~v;
+    }
+    bool ok = !ord.empty();
+    for (int32_t x : ord) ok &= x != INT32_MIN;
+    if (ok) {
+        sch->round.push_back((uint32_t)cx.rounds);
+        sch->v.insert(sch->v.end(), ord.begin(), ord.end());
+        sch->off.push_back((uint32_t)sch->v.size());
+        sch->extended = true;
+    }
+    return 0;
+}
+
+// the control word with the mailboxes' maxima (the last two rounds' were never
+// counted by k_tcp_window), the schedule's extension and the cache's ranks back
+static int collect_control(const Glob& g, shd_pc* pc, int32_t V, TcpSched* sch, shd_tcp_result* res) {
+    std::vector<uint32_t> nm(2 * (kMailSub + 1));
+    HCHECK(hipMemcpy(nm.data(), g.nmail, sizeof(uint32_t) * nm.size(), hipMemcpyDeviceToHost));
+    TCtl cx;
+    HCHECK(hipMemcpy(&cx, g.ctl, sizeof(TCtl), hipMemcpyDeviceToHost));
+    res->max_round_deliveries = cx.max_mail;
+    res->max_round_overflow = cx.max_ovf;
+    if (cx.ft_bad) res->error |= SHD_TCP_ERR_FIRST_TOUCH;
+    if (cx.ft_bad && sch && pc && g.world == 1 && sch->round.size() < kFtReruns) TRY(sched_extend(g, cx, V, sch));
+    res->error |= cx.xerr;
+    if (pc && !cx.ft_bad) {   // the cache's ranks as the serial run leaves them
+        std::vector<int32_t> old_rank(pc->h_rank, pc->h_rank + V), old_self(pc->h_self_rank, pc->h_self_rank + V);
+        HCHECK(hipMemcpy(pc->h_rank, g.rank, sizeof(int32_t) * (size_t)V, hipMemcpyDeviceToHost));
+        HCHECK(hipMemcpy(pc->h_self_rank, g.srank, sizeof(int32_t) * (size_t)V, hipMemcpyDeviceToHost));
+        HCHECK(hipMemcpy(&pc->next_rank, g.next_rank, sizeof(int32_t), hipMemcpyDeviceToHost));
+        // and minimumPathLatency with the entries those rows stored
+        TRY(shd_pc_fold_ranked(pc, old_rank.data(), old_self.data()));
+    }
+    for (int b = 0; b < 2; b++) {
+        uint64_t sum = 0;
+        for (uint32_t j = 0; j <= kMailSub; j++) {
+            const uint32_t cap = j < kMailSub ? g.mail_part : g.mail_cap - g.mail_part * kMailSub;
+            const uint32_t v = nm[b * (kMailSub + 1) + j];
+            sum += v < cap ? v : cap;
+            if (j == kMailSub && (v < cap ? v : cap) > res->max_round_overflow) res->max_round_overflow = v < cap ? v : cap;
+        }
+        if (sum > res->max_round_deliveries) res->max_round_deliveries = sum;
+    }
+    return 0;
+}
+
+// the per-host scalars and the run's totals
+static int collect_host_scalars(const std::vector<DHost>& hout, shd_tcp_result* res) {
+    const size_t nloc = hout.size();
+    TRY(res_alloc(&res->next_event_id, nloc));
+    TRY(res_alloc(&res->next_packet_id, nloc));
+    TRY(res_alloc(&res->rng_probe, nloc));
+    for (size_t i = 0; i < nloc; i++) {
         res->next_event_id[i] = hout[i].ev_seq;
         res->next_packet_id[i] = hout[i].pkt_seq;
         uint32_t st = hout[i].rng;
@@ -4894,95 +5031,152 @@ static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, s
         res->error |= hout[i].err;
         res->max_host_sockets = std::max<uint32_t>(res->max_host_sockets, (uint32_t)hout[i].nsock);
     }
-    if (g.hrec) {   // the local hosts' records in one copy; the host names them and reads the queue's last length
-        const auto t0 = std::chrono::steady_clock::now();
-        resx->hosts = (shd_tcp_hostrec*)malloc(sizeof(shd_tcp_hostrec) * (size_t)(nloc ? nloc : 1));
-        if (!resx->hosts) { rc = -12; goto done; }
-        HCHECK(hipMemcpy(resx->hosts, g.hrec, sizeof(shd_tcp_hostrec) * (size_t)nloc, hipMemcpyDeviceToHost));
-        for (int32_t i = 0; i < nloc; i++) {
-            resx->hosts[i].host = h0 + i;
-            resx->hosts[i].depth_end = hout[i].cq_n;
-        }
-        resx->n_hosts = (uint64_t)nloc;
-        if (getenv("SHD_TCP_HOST_TIMING"))   // the copy's size and host wall time, for measurements
-            fprintf(stderr, "shd_tcp_run: %d host records (%zu bytes) copied in %.3f ms\n", nloc,
-                    sizeof(shd_tcp_hostrec) * (size_t)nloc, ms_since(t0));
+    return 0;
+}
+
+// the local hosts' records in one copy; the host names them and reads the queue's last length
+static int collect_host_records(const Glob& g, const std::vector<DHost>& hout, TcpResultX* resx) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const int32_t nloc = g.nloc;
+    TRY(res_alloc(&resx->hosts, (size_t)nloc));
+    HCHECK(hipMemcpy(resx->hosts, g.hrec, sizeof(shd_tcp_hostrec) * (size_t)nloc, hipMemcpyDeviceToHost));
+    for (int32_t i = 0; i < nloc; i++) {
+        resx->hosts[i].host = g.h0 + i;
+        resx->hosts[i].depth_end = hout[i].cq_n;
     }
-    if (g.path_on && pc && !res->error) {
-        // Path.packetCount (topology_incrementPathPacketCounter, worker.c:296):
-        // the cache's own counter, keyed on the unordered attached pair as
-        // shd_pc_count_packet keys it, takes each pair's sends.  A run that a
-        // rerun follows ended with SHD_TCP_ERR_FIRST_TOUCH and folds nothing.
-        for (uint64_t i = 0; i < resx->n_paths; i++) {
-            const shd_tcp_path& r = resx->paths[i];
-            if (r.packets_sent) shd_pc_add_packets(pc, pc->h_att_index[r.v_src], pc->h_att_index[r.v_dst], r.packets_sent);
-        }
+    resx->n_hosts = (uint64_t)nloc;
+    if (getenv("SHD_TCP_HOST_TIMING"))   // the copy's size and host wall time, for measurements
+        fprintf(stderr, "shd_tcp_run: %d host records (%zu bytes) copied in %.3f ms\n", nloc,
+                sizeof(shd_tcp_hostrec) * (size_t)nloc, ms_since(t0));
+    return 0;
+}
+
+// the tracker counters of every heartbeat, per host
+static int collect_node_counters(const Glob& g, const std::vector<DHost>& hout, shd_tcp_result* res) {
+    const size_t n = 2 * kTrk * (size_t)g.nloc * g.node_k;
+    res->node_k = g.node_k;
+    TRY(res_alloc(&res->n_heartbeats, (size_t)g.nloc));
+    TRY(res_alloc(&res->node_counters, n));
+    HCHECK(hipMemcpy(res->node_counters, g.node, sizeof(uint64_t) * n, hipMemcpyDeviceToHost));
+    for (int32_t i = 0; i < g.nloc; i++) res->n_heartbeats[i] = hout[i].nhb < g.node_k ? hout[i].nhb : g.node_k;
+    return 0;
+}
+
+// the [STATUS] lines, host by host, each host's records in its order
+static int collect_lines(const Glob& g, const std::vector<DHost>& hout, shd_tcp_result* res) {
+    std::string text;
+    std::vector<TRec> recs;
+    std::vector<int32_t> sk;
+    for (int32_t i = 0; i < g.nloc; i++) {
+        recs.resize(hout[i].ntr);
+        sk.resize(hout[i].ntrs + 1);
+        if (hout[i].ntr)
+            HCHECK(hipMemcpy(recs.data(), g.tr + (size_t)i * kTr, sizeof(TRec) * hout[i].ntr, hipMemcpyDeviceToHost));
+        if (hout[i].ntrs)
+            HCHECK(hipMemcpy(sk.data(), g.trs + (size_t)i * kTrSack, sizeof(int32_t) * hout[i].ntrs, hipMemcpyDeviceToHost));
+        order_iter_clears(recs);
+        for (const TRec& t : recs) format_line(text, t, sk.data() + t.sack_off, g.h0 + i);
+        res->n_lines += hout[i].ntr;
     }
-    if (g.node) {
-        res->node_k = g.node_k;
-        res->n_heartbeats = (uint32_t*)calloc(nloc, sizeof(uint32_t));
-        res->node_counters = (uint64_t*)malloc(sizeof(uint64_t) * 2 * kTrk * (size_t)nloc * g.node_k);
-        HCHECK(hipMemcpy(res->node_counters, g.node, sizeof(uint64_t) * 2 * kTrk * (size_t)nloc * g.node_k,
-                         hipMemcpyDeviceToHost));
-        for (int32_t i = 0; i < nloc; i++) res->n_heartbeats[i] = hout[i].nhb < g.node_k ? hout[i].nhb : g.node_k;
-    }
-    if (g.trace) {
-        std::string text;
-        std::vector<TRec> recs;
-        std::vector<int32_t> sk;
-        for (int32_t i = 0; i < nloc; i++) {
-            recs.resize(hout[i].ntr);
-            sk.resize(hout[i].ntrs + 1);
-            if (hout[i].ntr)
-                HCHECK(hipMemcpy(recs.data(), g.tr + (size_t)i * kTr, sizeof(TRec) * hout[i].ntr, hipMemcpyDeviceToHost));
-            if (hout[i].ntrs)
-                HCHECK(hipMemcpy(sk.data(), g.trs + (size_t)i * kTrSack, sizeof(int32_t) * hout[i].ntrs, hipMemcpyDeviceToHost));
-            order_iter_clears(recs);
-            for (const TRec& r : recs) format_line(text, r, sk.data() + r.sack_off, h0 + i);
-            res->n_lines += hout[i].ntr;
-        }
-        res->lines = (char*)malloc(text.size() + 1);
-        memcpy(res->lines, text.data(), text.size());
-        res->lines[text.size()] = 0;
-        res->len = text.size();
-    }
+    TRY(res_alloc(&res->lines, text.size() + 1));
+    memcpy(res->lines, text.data(), text.size());
+    res->lines[text.size()] = 0;
+    res->len = text.size();
+    return 0;
+}
+
 #ifdef SHD_TCP_PROF
-    {   // the steps' cycles summed over hosts, and per round the busiest lane
-        std::vector<uint64_t> pf(2 * kProf * (size_t)nloc);
-        std::vector<uint32_t> pr(2 * kProfRounds);
-        HCHECK(hipMemcpy(pf.data(), g.prof, sizeof(uint64_t) * pf.size(), hipMemcpyDeviceToHost));
-        HCHECK(hipMemcpy(pr.data(), g.prof_round, sizeof(uint32_t) * pr.size(), hipMemcpyDeviceToHost));
-        static const char* kName[kProf] = {"ingest", "evq_pop", "HEARTBEAT", "REFILL", "REFILL_LO", "PSTART",
-                                           "NOTIFY", "DELIVER", "DELACK", "RTO", "CLOSE", "WINUPD", "LOCAL",
-                                           "-", "lane_round", "max_ev", "-", "-", "-", "-"};
-        fprintf(stderr, "tcp_prof: step cycles_total count cycles_per\n");
-        for (uint32_t j = 0; j < kProf; j++) {
-            uint64_t cy = 0, n = 0;
-            for (int32_t i = 0; i < nloc; i++) {
-                const uint64_t* q = pf.data() + (size_t)i * 2 * kProf;
-                if (j == 15) { cy = std::max(cy, q[j]); continue; }
-                cy += q[j]; n += q[kProf + j];
-            }
-            if (cy || n) fprintf(stderr, "tcp_prof: %s %llu %llu %.1f\n", kName[j], (unsigned long long)cy,
-                                 (unsigned long long)n, n ? (double)cy / (double)n : 0.0);
+// the steps' cycles summed over hosts, and per round the busiest lane
+static int collect_prof(const Glob& g, uint64_t rounds) {
+    const int32_t nloc = g.nloc;
+    std::vector<uint64_t> pf(2 * kProf * (size_t)nloc);
+    std::vector<uint32_t> pr(2 * kProfRounds);
+    HCHECK(hipMemcpy(pf.data(), g.prof, sizeof(uint64_t) * pf.size(), hipMemcpyDeviceToHost));
+    HCHECK(hipMemcpy(pr.data(), g.prof_round, sizeof(uint32_t) * pr.size(), hipMemcpyDeviceToHost));
+    static const char* kName[kProf] = {"ingest", "evq_pop", "HEARTBEAT", "REFILL", "REFILL_LO", "PSTART",
+                                       "NOTIFY", "DELIVER", "DELACK", "RTO", "CLOSE", "WINUPD", "LOCAL",
+                                       "-", "lane_round", "max_ev", "-", "-", "-", "-"};
+    fprintf(stderr, "tcp_prof: step cycles_total count cycles_per\n");
+    for (uint32_t j = 0; j < kProf; j++) {
+        uint64_t cy = 0, n = 0;
+        for (int32_t i = 0; i < nloc; i++) {
+            const uint64_t* q = pf.data() + (size_t)i * 2 * kProf;
+            if (j == 15) { cy = std::max(cy, q[j]); continue; }
+            cy += q[j]; n += q[kProf + j];
         }
-        const uint64_t nr = std::min<uint64_t>(hctl.rounds, kProfRounds);
-        for (uint64_t r = 0; r < nr; r++)
-            fprintf(stderr, "tcp_round: %llu max_ev %u max_kcyc %u\n", (unsigned long long)r, pr[r], pr[kProfRounds + r]);
+        if (cy || n) fprintf(stderr, "tcp_prof: %s %llu %llu %.1f\n", kName[j], (unsigned long long)cy,
+                             (unsigned long long)n, n ? (double)cy / (double)n : 0.0);
     }
+    const uint64_t nr = std::min<uint64_t>(rounds, kProfRounds);
+    for (uint64_t k = 0; k < nr; k++)
+        fprintf(stderr, "tcp_round: %llu max_ev %u max_kcyc %u\n", (unsigned long long)k, pr[k], pr[kProfRounds + k]);
+    return 0;
+}
 #endif
+
+static int tcp_collect(TcpRun& run, const shd_tcp_model* m, const TcpPlan& p, shd_comm* comm, TcpSched* sch) {
+    const TcpRun& r = run;
+    const Glob& g = r.g;
+    shd_pc* pc = m->path_cache;
+    TcpResultX* resx = r.resx;
+    shd_tcp_result* res = &resx->pub;
+    std::vector<DHost> hout(g.nloc);
+    HCHECK(hipMemcpy(hout.data(), g.host, sizeof(DHost) * g.nloc, hipMemcpyDeviceToHost));
+    TRY(collect_queries(r, comm, res));
+    res->first_host = g.h0;
+    res->n_local_hosts = g.nloc;
+    res->rounds = run.live.hctl.rounds;
+    if (g.flow_on) TRY(collect_flows(r, run.live.ser, p.so[p.nloc], resx));
+    if (g.path_on) TRY(collect_paths(r, m, p, resx));
+    if (p.any_pcap) TRY(collect_pcap(r.live.pcp, g.nloc, res));
+    TRY(collect_control(g, pc, p.V, sch, res));
+    TRY(collect_host_scalars(hout, res));
+    if (g.hrec) TRY(collect_host_records(g, hout, resx));
+    if (g.path_on && pc && !res->error) collect_path_packets(pc, resx);
+    if (g.node) TRY(collect_node_counters(g, hout, res));
+    if (g.trace) TRY(collect_lines(g, hout, res));
+#ifdef SHD_TCP_PROF
+    TRY(collect_prof(g, run.live.hctl.rounds));
+#endif
+    return 0;
+}
+
+// shd_tcp_run on one engine (comm null) or on this engine's share of a group
+// (shd_tcp_run_group: hosts [h0, h0 + nloc), the round's window agreed over
+// the group, deliveries between engines exchanged after every round), in
+// phases:
+//   plan     tcp_plan: what the model alone decides, and every refusal; no
+//            device but path_cache mode's window
+//   open     the device's workspace, locked for the run, and the result
+//            (TcpRun; its close() is the one way out, whatever fails)
+//   setup    tcp_setup: Glob and the buffers behind it, part by part; Glob
+//            is complete before the stream's first use and read-only after
+//   rounds   tcp_rounds: one engine's captured batches or the group's round
+//            of collectives, the captures and samples drained as they go
+//   collect  tcp_collect: the result, one part per function
+//   close    the stream and graph destroyed, the workspace freed unless kept
+static int tcp_run_impl(const shd_tcp_model* m, shd_comm* comm, int32_t trace, shd_tcp_result** out,
+                        TcpSched* sch = nullptr) {
+    const auto t_call = std::chrono::steady_clock::now();
+    if (!out) return -22;
+    TcpPlan plan;
+    TRY(tcp_plan(m, comm ? comm->world : 1, comm ? comm->rank : 0, plan));
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kWsDevices) return -5;
+    TcpRun run(g_ws[dev]);
+    TRY(res_alloc(&run.resx, 1));
+    memset(run.resx, 0, sizeof(TcpResultX));
+    shd_tcp_result* res = &run.resx->pub;   // (the struct's first member: freed through it)
+    res->max_host_procs = plan.max_procs;
+    res->sock_bytes = sizeof(DSock) * (uint64_t)plan.so[plan.nloc];
+    TRY(tcp_setup(run, m, plan, trace, sch));
+    res->setup_ms = ms_since(t_call);
+    TRY(tcp_rounds(run, comm, res));
+    const auto t_results = std::chrono::steady_clock::now();
+    TRY(tcp_collect(run, m, plan, comm, sch));
     res->results_ms = ms_since(t_results);
-done:
     const auto t_free = std::chrono::steady_clock::now();
-    if (d_sched) (void)hipFree(d_sched);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (gexec) (void)hipGraphExecDestroy(gexec);
-    if (graph) (void)hipGraphDestroy(graph);
-    if (st) (void)hipStreamDestroy(st);
-    if (!ws_keep || rc) ws_free_all(ws);   // a failed run leaves no workspace behind
-    ws_lock.unlock();
-    if (rc) { shd_tcp_result_free(res); return rc; }
+    run.close(false);
     res->teardown_ms = ms_since(t_free);
     *out = res;
     return 0;
