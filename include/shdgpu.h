@@ -179,9 +179,12 @@ typedef struct shd_pc_info {
     int32_t prefer_direct;
     int32_t rows_computed;          /* rows built (0 in pure direct mode)      */
     int64_t n_ties;                 /* vertices whose shortest-path parent was not unique */
-    int32_t max_hops;               /* longest shortest path (edges)           */
-    int32_t sssp_iterations_max;    /* deepest frontier iteration count        */
-    int32_t n_unroutable;           /* row entries with no path (self without self-loop) */
+    int32_t max_hops;               /* most edges on a row entry's path between two different
+                                       attached vertices (the [src] self entry counts none) */
+    int32_t sssp_iterations_max;    /* deepest frontier iteration count (an iteration advances the
+                                       frontier one hop: past max_hops when every row ran it) */
+    int32_t n_unroutable;           /* row entries with no path, over all rows: (-1, -1) in the
+                                       table (the self entry of a vertex without a self-loop) */
     double min_latency_ms;          /* min over all table latencies (topology.c:1374-1378) */
     double build_ms_device;         /* device time of the table build (HIP events) */
     double build_ms_sssp;           /* device time of the SSSP-row kernel alone */
@@ -196,8 +199,17 @@ typedef struct shd_pc_info {
                                        whole-number weights whose probe rows (2 x CUs) were
                                        90 % tied (round 6; their ties counted in the second
                                        pass, sssp_iterations_max over the probe only) */
-    int32_t _pad0;
+    int32_t first_pass_kernel;      /* SHD_PC_K_*: the row kernel shd_pc_build picked for the
+                                       first pass (by V and the LDS budget); how tests pin
+                                       the dispatch windows */
 } shd_pc_info;
+
+/* shd_pc_info.first_pass_kernel */
+#define SHD_PC_K_NONE 0          /* no rows built (direct mode) */
+#define SHD_PC_K_ROWS_LDS_256 1  /* k_sssp_rows_lds<256>: V <= 2048 */
+#define SHD_PC_K_ROWS2_LDS 2     /* k_sssp_rows2_lds: two rows per workgroup, V <= 10 080 */
+#define SHD_PC_K_ROWS_LDS_1024 3 /* k_sssp_rows_lds<1024>: one row per workgroup, V <= 11 701 */
+#define SHD_PC_K_ROWS_GLOBAL 4   /* k_sssp_rows_global: the row arrays in global scratch */
 
 /* attached: vertex ids with >=1 attached host (topology.c:2393, verticesWithAttachedHosts) */
 int shd_pc_create(const shd_graph* g, const int32_t* attached, int32_t n_attached,

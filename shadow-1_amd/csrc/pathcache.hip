@@ -618,9 +618,10 @@ __device__ void sssp_one_row(int32_t row, int32_t src, int32_t V, int32_t T,
     // taking the parent's depth + 1 (the level the per-level passes of round 1
     // gave it).  Its product is written before its depth (a workgroup release
     // between them), and readers read the depth first, through volatile LDS
-    // accesses, so a done parent's product is its final one.  A chain of L
-    // hops needs at most L sweeps of its vertices' threads; threads never
-    // wait on each other, so some vertex finishes in every round of sweeps.
+    // accesses, so a done parent's product is its final one.  A thread never
+    // blocks: it passes over a vertex whose parent is not done and comes back,
+    // so some vertex finishes in every round of every thread's sweeps; how
+    // many sweeps one thread makes meanwhile depends on the waves' pace.
     {
         volatile uint16_t* vupd = upd;
         volatile uint64_t* vdist = dist;
@@ -639,9 +640,25 @@ __device__ void sssp_one_row(int32_t row, int32_t src, int32_t V, int32_t T,
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                 vupd[v] = (uint16_t)(du + 1);
             }
-            if (sweep > V) {   // cannot be: a parent chain longer than the graph
-                atomicAdd((unsigned long long*)&stats[4], 1ull);
-                break;
+            if (left && sweep > V) {
+                // More sweeps than the graph has vertices.  On a deep tree (a chain
+                // of hundreds of hops) that is a thread whose vertices wait for other
+                // waves' levels: its sweeps cost less than theirs, so their number
+                // says nothing.  The exact test instead: from each vertex still to
+                // do, its ancestors reach a finished vertex within V steps unless the
+                // parents do not form a tree (cannot be), and only then give up.
+                bool stuck = false;
+                for (int32_t v = tid; v < V && !stuck; v += BLOCK) {
+                    if (vupd[v] != kTodo) continue;
+                    int32_t u = parent[v], n = 0;
+                    while (n <= V && vupd[u] == kTodo) { u = parent[u]; n++; }
+                    stuck = n > V || vupd[u] == kNever;
+                }
+                if (stuck) {
+                    atomicAdd((unsigned long long*)&stats[4], 1ull);
+                    break;
+                }
+                sweep = 0;
             }
         }
     }
@@ -2346,12 +2363,14 @@ static int pc_build(shd_pc* pc, shd_comm* comm) {
         bool lo = false;
         int64_t cnt_from = INT64_MAX;   // (a predicted all-tied build: the tie list's unprobed rows)
         pc->info.n_tie_rows_predicted = 0;
+        pc->info.first_pass_kernel = SHD_PC_K_NONE;
         const size_t lds_rows = lds_bytes_for(V), lds = lds_launch_bytes(pc, &lo);
         int ncu = 256;
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, pc->device) == hipSuccess) ncu = prop.multiProcessorCount;
         if (lds_rows <= kLdsMax) {
             if (V <= 2048) {
+                pc->info.first_pass_kernel = SHD_PC_K_ROWS_LDS_256;
                 int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, kLdsMax / lds));
                 int grid = std::max(1, std::min(row1 - row0, ncu * per_cu));
                 SHD_HIP(hipFuncSetAttribute((const void*)k_sssp_rows_lds<256>,
@@ -2365,6 +2384,7 @@ static int pc_build(shd_pc* pc, shd_comm* comm) {
                                (const char*)nullptr, 0, (const uint8_t*)nullptr, 0);
             } else if (two_row_ok(pc)) {
                 // two rows per workgroup (sssp_bf2), row B parked in d_scratch
+                pc->info.first_pass_kernel = SHD_PC_K_ROWS2_LDS;
                 const size_t lds2 = two_row_lds(V);
                 const int grid = std::max(1, std::min((row1 - row0 + 1) / 2, ncu));
                 const size_t park = (size_t)grid * V * sizeof(uint64_t);
@@ -2413,6 +2433,7 @@ static int pc_build(shd_pc* pc, shd_comm* comm) {
                     }
                 }
             } else {
+                pc->info.first_pass_kernel = SHD_PC_K_ROWS_LDS_1024;
                 int grid = std::max(1, std::min(row1 - row0, ncu));
                 SHD_HIP(hipFuncSetAttribute((const void*)k_sssp_rows_lds<kRowBlock>,
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -2426,6 +2447,7 @@ static int pc_build(shd_pc* pc, shd_comm* comm) {
             }
         } else {
             const size_t per_block = ((size_t)14 * V + 255) & ~(size_t)255;
+            pc->info.first_pass_kernel = SHD_PC_K_ROWS_GLOBAL;
             int grid = std::max(1, std::min(row1 - row0, ncu * 4));
             if (!pc->d_scratch || pc->scratch_bytes < per_block * grid) {
                 if (pc->d_scratch) (void)hipFree(pc->d_scratch);
@@ -2706,6 +2728,10 @@ static int pc_lookup_at(shd_pc* pc, int32_t a, int32_t b, double* lat, double* r
         // self pair: stored by row a ([a] with the self-loop) or by the
         // self-path computation, whichever came first
         int32_t ra = pc->h_rank[a], rs = pc->h_self_rank[a];
+        // row a stores its [a] entry only over a self-loop (without one
+        // computePathProperties fails, topology.c:1490-1495, and nothing is
+        // stored): the pair then misses until the self path is computed
+        if (pc->h_self_eid[a] < 0) ra = kNoRank;
         if (ra == kNoRank && rs == kNoRank) {
             pc->h_self_rank[a] = rs = pc->next_rank++;
             int rc = fetch2(pc, pc->d_self, (size_t)a, lat, rel);
@@ -2818,6 +2844,7 @@ extern "C" int shd_pc_lookup_batch(shd_pc* pc, const int32_t* src_vertex, const 
         if (pc->complete || adj) { kind[i] = kPvDir; idx[i] = (uint64_t)a * T + b; continue; }
         if (a == b) {
             int32_t ra = pc->h_rank[a], rs = pc->h_self_rank[a];
+            if (pc->h_self_eid[a] < 0) ra = kNoRank;   // (row a stored no [a] entry: pc_lookup_at)
             if (ra == kNoRank && rs == kNoRank) pc->h_self_rank[a] = rs = pc->next_rank++;
             if (rs < ra) { kind[i] = kPvSelf; idx[i] = (uint64_t)a; }
             else { kind[i] = kPvRow; idx[i] = (uint64_t)a * T + a; }

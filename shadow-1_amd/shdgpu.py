@@ -98,8 +98,12 @@ class PcInfo(C.Structure):
         ("build_ms_device", C.c_double), ("build_ms_sssp", C.c_double),
         ("build_ms_props", C.c_double), ("build_ms_direct", C.c_double),
         ("n_tie_rows", C.c_int32), ("n_tie_rows_global", C.c_int32),
-        ("n_tie_rows_predicted", C.c_int32), ("_pad0", C.c_int32),
+        ("n_tie_rows_predicted", C.c_int32), ("first_pass_kernel", C.c_int32),
     ]
+
+
+# shd_pc_info.first_pass_kernel (include/shdgpu.h SHD_PC_K_*)
+SHD_PC_K_NONE, SHD_PC_K_ROWS_LDS_256, SHD_PC_K_ROWS2_LDS, SHD_PC_K_ROWS_LDS_1024, SHD_PC_K_ROWS_GLOBAL = range(5)
 
 
 class UdpApp(C.Structure):

@@ -113,11 +113,17 @@ def test_pc_info_layout_matches_the_header(tmp_path):
     import ctypes as C
     src = tmp_path / "p.c"
     src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "%s/include/shdgpu.h"\n'
-                   'int main(void){printf("%%zu %%zu %%zu %%zu\\n", sizeof(shd_pc_info),'
+                   'int main(void){printf("%%zu %%zu %%zu %%zu %%zu\\n", sizeof(shd_pc_info),'
                    ' offsetof(shd_pc_info, n_tie_rows), offsetof(shd_pc_info, n_tie_rows_global),'
-                   ' offsetof(shd_pc_info, n_tie_rows_predicted));return 0;}\n' % REPO)
+                   ' offsetof(shd_pc_info, n_tie_rows_predicted), offsetof(shd_pc_info, first_pass_kernel));'
+                   'printf("%%d %%d %%d %%d %%d\\n", SHD_PC_K_NONE, SHD_PC_K_ROWS_LDS_256, SHD_PC_K_ROWS2_LDS,'
+                   ' SHD_PC_K_ROWS_LDS_1024, SHD_PC_K_ROWS_GLOBAL);return 0;}\n' % REPO)
     exe = tmp_path / "p"
     subprocess.run(["gcc", str(src), "-o", str(exe)], check=True)
     got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
     assert got == [C.sizeof(S.PcInfo), S.PcInfo.n_tie_rows.offset, S.PcInfo.n_tie_rows_global.offset,
-                   S.PcInfo.n_tie_rows_predicted.offset]
+                   S.PcInfo.n_tie_rows_predicted.offset, S.PcInfo.first_pass_kernel.offset,
+                   S.SHD_PC_K_NONE, S.SHD_PC_K_ROWS_LDS_256, S.SHD_PC_K_ROWS2_LDS, S.SHD_PC_K_ROWS_LDS_1024,
+                   S.SHD_PC_K_ROWS_GLOBAL]
+    # first_pass_kernel took the padding slot after n_tie_rows_predicted: the struct kept its size
+    assert got[0] == 104 and got[4] == 100

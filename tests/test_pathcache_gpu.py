@@ -11,6 +11,7 @@ import pytest
 import oracle_ffi as O
 import shdgpu as S
 import workloads as W
+from pc_graphs import directed_geo as _directed_geo
 from pc_helpers import PathCache, same_bits
 
 pytestmark = pytest.mark.gpu
@@ -231,16 +232,6 @@ def test_tie_graph_lazy_lookup_matches_reference_cache():
         a = pc.lookup(s, d)
         b = ot.get(s, d)
         assert np.array(a).view(np.uint64).tolist() == np.array(b).view(np.uint64).tolist(), (s, d)
-
-
-def _directed_geo(V, seed):
-    g0 = W.geometric_graph(V, seed=seed, loss_max=0.01)
-    src, dst = g0.src.astype(np.int64), g0.dst.astype(np.int64)
-    nsl = src != dst
-    rng = np.random.default_rng(seed)
-    return S.GraphArrays(V, np.concatenate([src, dst[nsl]]), np.concatenate([dst, src[nsl]]),
-                         np.concatenate([g0.latency, g0.latency[nsl] * (1.0 + rng.random(int(nsl.sum())))]),
-                         np.concatenate([g0.loss, g0.loss[nsl]]), directed=True)
 
 
 @pytest.mark.parametrize("name", ["geo", "grid", "directed", "bundled", "prefer_direct"])
