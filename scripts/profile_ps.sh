@@ -5,6 +5,9 @@
 #   the SQ counters per wave and round over the bench's timed region (two counter sets, no tracing),
 #   the kernel trace of the timed region against the bench's own time per round.
 #     scripts/profile_ps.sh <out dir> [<product library>] [<timing library>]
+# PS_TIMING_ARGS goes to scripts/ps_timing.py ("--convention events+1" for a timing library built with
+# -DSHD_NO_EXIT1, whose iteration count has the loop's empty last pass in it; "--exit" for one built
+# with -DSHD_TIMING_EXIT).
 set -o pipefail
 export TMPDIR=/tmp
 O=$1
@@ -12,7 +15,7 @@ LIB=${2:-shadow-1_amd/libshdgpu.so}
 TIM=${3:-shadow-1_amd/libshdgpu_tim.so}
 B="bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --lossy-edge-loss-max 0"
 rm -rf $O; mkdir -p $O
-SHDGPU_LIB=$TIM timeout -k 10 200 python3 -u scripts/ps_timing.py > $O/stamps_c3.txt 2>&1 || { tail -5 $O/stamps_c3.txt; exit 3; }
+SHDGPU_LIB=$TIM timeout -k 10 200 python3 -u scripts/ps_timing.py $PS_TIMING_ARGS > $O/stamps_c3.txt 2>&1 || { tail -5 $O/stamps_c3.txt; exit 3; }
 i=0
 for set in "SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS" \
            "SQ_WAVES SQ_INSTS_SMEM SQ_INSTS_BRANCH SQ_BUSY_CYCLES SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VALU"; do

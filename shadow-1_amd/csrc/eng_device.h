@@ -2198,12 +2198,24 @@ __device__ __forceinline__ void arrival_fast(const DParams& P, HostCtx& c, uint3
 // general iteration.  The choice is per lane: per wave, by one ballot, so that
 // one lane that cannot sends the wave's iteration the general way, measured
 // no better.
-__device__ __forceinline__ bool steady_iter(const DParams& P, HostCtx& c, uint64_t we, uint32_t& st) {
+//
+// CARRIED (the loop that leaves in the iteration of its last event,
+// ps_loop_close): `ct` is the lane's candidate time, next_cand() of the state
+// the previous iteration left, for the lanes in state 0 -- all of them before
+// `we`, the others were retired where it was worked out -- so the minimum is
+// not taken again here and no lane ends here.
+// (next_cand: the earliest of the lane's five candidate times, take_next's t)
+__device__ __forceinline__ uint64_t next_cand(const HostCtx& c) {
     const uint64_t ht = c.evq_n ? c.top_time : kInf;
     const uint64_t m01 = c.tt0 < c.tt1 ? c.tt0 : c.tt1;
     const uint64_t bt = m01 < c.tt2 ? m01 : c.tt2;
     const uint64_t qt = c.dt < ht ? c.dt : ht;
-    const uint64_t t = bt < qt ? bt : qt;
+    return bt < qt ? bt : qt;
+}
+template <bool CARRIED = false>
+__device__ __forceinline__ bool steady_iter(const DParams& P, HostCtx& c, uint64_t we, uint32_t& st, uint64_t ct = 0) {
+    const uint64_t ht = c.evq_n ? c.top_time : kInf;
+    const uint64_t t = CARRIED ? ct : next_cand(c);
     const uint32_t neq = (uint32_t)(c.tt0 == t) + (uint32_t)(c.tt1 == t) + (uint32_t)(c.tt2 == t) +
                          (uint32_t)(c.dt == t) + (uint32_t)(ht == t);
     const bool u = st == 0u && t < we && neq == 1u;
@@ -2221,7 +2233,7 @@ __device__ __forceinline__ bool steady_iter(const DParams& P, HostCtx& c, uint64
     const bool sa = u && c.dt == t && d.kind == SHD_EV_PACKET && arrival_fast_ok(P, c);
     const bool sn = u && c.tt2 == t && notify_fast_ok_room(P, c, room);
     const bool sr = u && c.tt1 == t && c.cq_count == 0 && c.tq_count == 0;
-    const bool end = st == 0u && t >= we;   // nothing left before the window's end: the lane is done
+    const bool end = !CARRIED && st == 0u && t >= we;   // nothing left before the window's end: the lane is done
     c.now = now0;
     const bool sdy = sa || sn || sr || end;
     if (!sdy) return false;

@@ -1142,16 +1142,42 @@ __device__ __forceinline__ void ps_prologue(const DParams& P, HostCtx& c, bool a
 // (pspan) names the window's non-empty bins.  The bins wholly consumed are reset as
 // in ps_prologue; their bits go to clr (bit j: bin b0 + j), cleared from the
 // bitmap loaded at this round's start once it has landed (ps_loop_close).
+//
+// AHEAD: the count starts at what the staging counted (du, pf_stage): the
+// first du.n0 events are before the previous window's end + the window, which
+// `we` is not below; when entry n0's time is not before `we` (no such entry:
+// kInf) that is the count, with no LDS read, and otherwise -- the window
+// starts later than the previous one ended -- the scan goes on behind it.  The
+// head's time is the staging's too.
+struct PfDue {
+    uint32_t n0;
+    uint64_t t0, th;   // kInf: none
+};
+template <bool AHEAD = false>
 __device__ __forceinline__ void ps_prologue_pf(const DParams& P, HostCtx& c, bool active, uint64_t ws, uint64_t we,
-                                               uint32_t pnd, uint32_t wbits, uint32_t& clr) {
+                                               uint32_t pnd, const PfDue& du, uint32_t wbits, uint32_t& clr) {
     const uint64_t b0 = ws >> P.bin_shift;
     const uint32_t nbin = (uint32_t)(((we - 1) >> P.bin_shift) - b0) + 1u;
     if (active) {
-        uint32_t nd = 0;
-        for (; nd < pnd; nd++)
-            if (s_due[nd * kBlock + threadIdx.x].time >= we) break;
-        c.nd = nd;
-        c.dt = nd ? s_due[threadIdx.x].time : kInf;
+        if (AHEAD) {
+            uint32_t nd = du.n0;
+            if (du.t0 < we)
+                for (nd++; nd < pnd; nd++)
+                    if (s_due[nd * kBlock + threadIdx.x].time >= we) break;
+            c.nd = nd;
+            c.dt = nd ? du.th : kInf;
+        } else {
+            uint32_t nd = 0;
+            for (; nd < pnd; nd++)
+                if (s_due[nd * kBlock + threadIdx.x].time >= we) break;
+            c.nd = nd;
+            c.dt = nd ? s_due[threadIdx.x].time : kInf;
+        }
+    }
+#ifdef SHD_TIMING_EXIT
+    TIMP(9);   // the fast round's due count and head known (slot 9 is free in a NOLOOP build)
+#endif
+    if (active) {
 #pragma unroll
         for (uint32_t j = 0; j < 3; j++) {
             const uint64_t b = b0 + j;
@@ -1199,13 +1225,32 @@ __device__ __forceinline__ void pf_issue(const PsRsrc& R, uint32_t lb, uint64_t 
 // the loaded bins' events in [lo, hi) into s_due, sorted (the round's due
 // list is spent); their count, or kDueCap + 1 when they do not fit (the next
 // round then reads its window as without prefetch)
-__device__ __forceinline__ uint32_t pf_stage(const PfBins& pb, uint64_t lo, uint64_t hi) {
+//
+// AHEAD: also, from the registers the events are staged from, what the next
+// round's prologue would find by reading the sorted list again (PfDue): the
+// number of staged events before `lim` -- a lower bound of the next window's
+// end, so they are all that round's, and the list's first n0 once it is sorted
+// -- the earliest time among the others (entry n0's) and the earliest of all
+// (the head's).
+template <bool AHEAD = false>
+__device__ __forceinline__ uint32_t pf_stage(const PfBins& pb, uint64_t lo, uint64_t hi, uint64_t lim, PfDue& du) {
     uint32_t nw = 0;
+    if (AHEAD) du = PfDue{0u, kInf, kInf};
 #pragma unroll
     for (uint32_t j = 0; j < kPfBins; j++) {
         if (((pb.m >> j) & 1u) == 0) continue;
 #pragma unroll
-        for (uint32_t k = 0; k < kBinCap; k++) due_add(pb.x[j][k], nw, lo, hi);
+        for (uint32_t k = 0; k < kBinCap; k++) {
+            due_add(pb.x[j][k], nw, lo, hi);
+            if (AHEAD) {
+                const uint64_t t = evv_time(pb.x[j][k]);
+                if (t >= lo && t < hi) {
+                    if (t < lim) du.n0++;
+                    else du.t0 = t < du.t0 ? t : du.t0;
+                    du.th = t < du.th ? t : du.th;
+                }
+            }
+        }
     }
     if (nw > (uint32_t)kDueCap) return (uint32_t)kDueCap + 1u;
     for (uint32_t i = 1; i < nw; i++) {
@@ -1268,7 +1313,19 @@ struct PsNoFin {
 #if defined(SHD_TIMING_LIGHT) && !defined(SHD_TIMING_NOLOOP)
 #define SHD_TIMING_INLOOP 1
 #endif
-template <bool PF, bool XCH = true, class Fin = PsNoFin, bool STEADY = false>
+// EXIT (the lean k_round_ps): the loop leaves in the iteration that
+// ran the wave's last event.  The lane's candidate time (next_cand) is worked
+// out before the loop and again at the bottom of every iteration, for the
+// lanes in state 0, from the state the iteration left -- behind the general
+// iteration and run_work, so nothing lies between its computation and its use
+// at the next iteration's top (a flush inside the loop runs when every lane is
+// in state 2 or 3, and the lanes it sets to 1 get a new candidate behind their
+// run_work) -- and a lane whose candidate is not before `we` (take_next's
+// test) is done there: the exit ballot fires in that iteration, without a
+// pass in which no lane runs an event, and a wave without an active lane
+// does not enter the loop.  steady_iter takes the carried candidate in place
+// of its own minimum.
+template <bool PF, bool XCH = true, class Fin = PsNoFin, bool STEADY = false, bool EXIT = false>
 __device__ __forceinline__ void ps_loop_close(const DParams& P, HostCtx& c, bool active, bool has, const PsRsrc& R,
                                               uint32_t lb, uint64_t we, uint32_t (&w)[kNBW], uint32_t clr_p,
                                               uint32_t clr, uint64_t& next, PfBins* pb, uint64_t* span,
@@ -1280,9 +1337,20 @@ __device__ __forceinline__ void ps_loop_close(const DParams& P, HostCtx& c, bool
     uint32_t n_it = 0, n_fl = 0;
     unsigned long long t_take = 0, t_work = 0, t_fl = 0, ta = 0, t_q[3] = {0, 0, 0};
 #endif
+#ifdef SHD_TIMING_EXIT   // (with SHD_TIMING_NOLOOP: slots 8 and 9 are free there)
+    unsigned long long tx = 0, t_empty = 0;
+    uint32_t ev0 = 0;
+    bool work = false;
+#endif
     {
         uint32_t st = active ? 0u : 3u;
+        uint64_t ct = 0;   // EXIT: the candidate time of a lane in state 0
+        if (EXIT) {
+            ct = next_cand(c);
+            if (st == 0u && ct >= we) st = 3u;
+        }
         for (;;) {
+            if (!EXIT || __ballot(st <= 1u) != 0)
             for (;;) {
 #ifdef SHD_TIMING_LIGHT
                 n_it++;
@@ -1290,8 +1358,13 @@ __device__ __forceinline__ void ps_loop_close(const DParams& P, HostCtx& c, bool
 #ifdef SHD_TIMING_INLOOP
                 ta = wall_clock64();
 #endif
+#ifdef SHD_TIMING_EXIT
+                tx = wall_clock64();
+                ev0 = c.c_events;
+                work = __ballot(st == 1u) != 0;
+#endif
                 bool sdy = false;
-                if (STEADY) sdy = steady_iter(P, c, we, st);
+                if (STEADY) sdy = steady_iter<EXIT>(P, c, we, st, ct);
                 if (st == 0u && !sdy) {
                     shd_event e;
 #ifdef SHD_TIMING_INLOOP
@@ -1351,6 +1424,14 @@ __device__ __forceinline__ void ps_loop_close(const DParams& P, HostCtx& c, bool
 #ifdef SHD_TIMING_INLOOP
                 t_work += wall_clock64() - ta;
 #endif
+                if (EXIT && st == 0u) {
+                    ct = next_cand(c);
+                    if (ct >= we) st = 3u;
+                }
+#ifdef SHD_TIMING_EXIT
+                // the pass in which no lane ran an event or worked (the parent's last one)
+                t_empty = (!work && __ballot(c.c_events != ev0) == 0) ? wall_clock64() - tx : 0;
+#endif
                 if (__ballot(st <= 1u) == 0) break;
             }
             const bool last = __ballot(st == 2u) == 0;
@@ -1385,8 +1466,14 @@ __device__ __forceinline__ void ps_loop_close(const DParams& P, HostCtx& c, bool
         TIMVP(16, (uint64_t)n_it);   // loop iterations of the wave
         TIMVP(17, (uint64_t)n_fl);   // flushes
         TIMVP(18, (uint64_t)__popcll(__ballot(active)));
+#ifdef SHD_TIMING_EXIT
+        TIMVP(8, t_empty + 1);   // the loop's last pass when no lane ran an event or worked in it (+ 1; 1: it did)
+#else
         TIMVP(8, t_take);    // in take_next + begin_event (+ the fused notification / refill)
+#endif
+#ifndef SHD_TIMING_EXIT
         TIMVP(9, t_work);    // in run_work
+#endif
         TIMVP(10, t_fl);     // in the flushes before the last
         TIMVP(11, t_q[0]);   // of 8: take_next
         TIMVP(15, t_q[1]);   //       begin_event
@@ -1630,6 +1717,21 @@ constexpr bool kPsSteady = true;
 constexpr bool kPsSteady = false;
 #endif
 
+// the event loop's two ends (the lean k_round_ps): the loop leaves with its
+// last event (ps_loop_close's EXIT), and the fast round takes its due count
+// and head from the staging (pf_stage, ps_prologue_pf); SHD_NO_EXIT1 /
+// SHD_NO_EXIT2 build the loop and the scan as they were, for an A/B
+#ifndef SHD_NO_EXIT1
+constexpr bool kPsExit = true;
+#else
+constexpr bool kPsExit = false;
+#endif
+#ifndef SHD_NO_EXIT2
+constexpr bool kPsDueAhead = true;
+#else
+constexpr bool kPsDueAhead = false;
+#endif
+
 template <bool LEAN>
 __global__ __launch_bounds__(kBlock) void k_round_ps(uint64_t window, int nb, DevSummary* __restrict__ ring,
                                                       const DevCtl* __restrict__ ctl, PsShare* __restrict__ shares,
@@ -1677,6 +1779,7 @@ __global__ __launch_bounds__(kBlock) void k_round_ps(uint64_t window, int nb, De
     uint64_t pf_b0 = 0;
     uint32_t pnd = 0, dirty = 0;
     uint64_t pspan = 0;
+    PfDue pdu{0, kInf, kInf};   // LEAN && kPsDueAhead: what pf_stage knows of the next window's due list
     for (int i = 0; i < nb; i++) {
         PS_PARAMS(i);
         const unsigned long long t_start = wall_clock64();
@@ -1707,7 +1810,7 @@ __global__ __launch_bounds__(kBlock) void k_round_ps(uint64_t window, int nb, De
             const uint32_t wbits = ps_window_bits(P, c, pspan, (uint32_t)((ws >> P.bin_shift) - pf_b0), ws, we);
             TIMP(1);
             active = has && !(host_next(c) >= we && wbits == 0);   // (no inbox: it would have been named)
-            ps_prologue_pf(P, c, active, ws, we, pnd, wbits, clr);
+            ps_prologue_pf<LEAN && kPsDueAhead>(P, c, active, ws, we, pnd, pdu, wbits, clr);
         } else {
             // the round's hand-off words: this parity's inbox count, the calendar bitmap
             uint32_t nin = 0;
@@ -1735,9 +1838,8 @@ __global__ __launch_bounds__(kBlock) void k_round_ps(uint64_t window, int nb, De
             nev = wave_sum_u32(c.c_events);
             npkt = wave_sum_u32(c.c_pkt);
         };
-        ps_loop_close<kPsPf, false, decltype(fin), LEAN && kPsSteady>(P, c, active, has, R, lb, we, w,
-                                                                      (uint32_t)(ws >> P.bin_shift) & (kNB - 1), clr, next, &pb,
-                                                                      &span, fin);
+        ps_loop_close<kPsPf, false, decltype(fin), LEAN && kPsSteady, LEAN && kPsSteady && kPsExit>(
+            P, c, active, has, R, lb, we, w, (uint32_t)(ws >> P.bin_shift) & (kNB - 1), clr, next, &pb, &span, fin);
         acc[2] += c.c_sent; acc[3] += c.c_idrop;
         const uint32_t pend = c.n_pend ? kPsPend : 0u;
         const uint32_t fl = wave_or_u32(c.err | pend);
@@ -1748,7 +1850,11 @@ __global__ __launch_bounds__(kBlock) void k_round_ps(uint64_t window, int nb, De
         TIMP(6);
         if (pfm) {   // the next window's events, staged while the other blocks finish
             const uint64_t b1 = we >> P.bin_shift;
-            pnd = pf_stage(pb, we, (b1 + kPfBins) << P.bin_shift);
+            // every staged event before lim is the next round's: its window ends at
+            // min(f_next + window, stop) and f_next >= we (the same clip as `we`)
+            uint64_t lim = we + window;
+            if (lim > stop || lim < we) lim = stop;
+            pnd = pf_stage<LEAN && kPsDueAhead>(pb, we, (b1 + kPfBins) << P.bin_shift, lim, pdu);
             pf_b0 = b1;
             pspan = span;
         }
