@@ -22,7 +22,11 @@ to a NOLOOP build (--exit here), slot 9 is the stamp of the fast round's due
 count and head known (1 -> 9: the scan of the staged list, or what is left of
 it) and slot 8 the time of the loop's last pass when no lane ran an event or
 worked in it (the pass the loop no longer makes: only a build with
--DSHD_NO_EXIT1 has such passes).
+-DSHD_NO_EXIT1 has such passes).  With -DSHD_TIMING_CARRY added to a NOLOOP
+build instead (--carry here), slot 9 is 1 + (the block's last flush had a near
+delivery under the far rule of ps_loop_close's CARRY: one whose stores the
+share waits for) + 2 x (it had a far one); a library built with -DSHD_NO_CARRY
+applies the same rule without acting on it.
 
 The iteration count (slot 16) follows the library: a loop that leaves with
 its last event (the default) counts the busiest lane's events, the loop built
@@ -54,6 +58,7 @@ def main():
                     help="what the library's iteration count is: the busiest lane's events (the default build) or one "
                          "more (-DSHD_NO_EXIT1, and the files under profiles/iter/)")
     ap.add_argument("--exit", action="store_true", help="the library is a -DSHD_TIMING_EXIT build (slots 8 and 9)")
+    ap.add_argument("--carry", action="store_true", help="the library is a -DSHD_TIMING_CARRY build (slot 9)")
     a = ap.parse_args()
     import torch
     torch.cuda.set_device(0)
@@ -156,6 +161,22 @@ def main():
               f"{np.mean([a.max() for a, _, _ in cr]):.2f} us; loop done -> there {np.mean([b.mean() for _, b, _ in cr]):.2f} us, "
               f"there -> close done {np.mean([c.mean() for _, _, c in cr]):.2f} us; publish drain (close done -> published) "
               f"mean {np.mean([d.mean() for d in dr]):.2f} / max {np.mean([d.max() for d in dr]):.2f} us")
+    # the last flush's deliveries under the far rule (--carry; slot 9: 1 + near + 2 x far), per
+    # block-round that flushed, and in the round's slowest block (the last to publish)
+    kinds, slow = [], []
+    for r in range(64 if a.carry else 0):
+        x = t_all[r]
+        t0 = x[:, 0].min()
+        ok = (t0 > 0) & (x[:, 21] >= x[:, 4]) & (x[:, 4] >= t0) & (x[:, 6] >= x[:, 21]) & (x[:, 9] >= 1) & (x[:, 9] <= 4)
+        if ok.any():
+            kinds += list(x[ok, 9] - 1)
+            slow.append(int(x[ok, 9][np.argmax(x[ok, 6])]) - 1)
+    if kinds:
+        kinds, slow = np.array(kinds), np.array(slow)
+        print(f"  last flush under the far rule: {len(kinds)} block-rounds, with a near delivery "
+              f"{np.mean((kinds & 1) != 0) * 100:.1f} %, with a far one {np.mean((kinds & 2) != 0) * 100:.1f} %, with "
+              f"none {np.mean(kinds == 0) * 100:.1f} %; the round's slowest block (the last to publish) had a near one "
+              f"in {int(((slow & 1) != 0).sum())} of {len(slow)} rounds ({np.mean((slow & 1) != 0) * 100:.1f} %)")
     # the close under the last flush's path loads (12 -> 23 -> 13), in blocks that flushed
     gp = []
     for r in range(64):

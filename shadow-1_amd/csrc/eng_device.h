@@ -1449,6 +1449,46 @@ __device__ __forceinline__ void flush_finish(const DParams& P, HostCtx& c, const
     emit_nocal<XCH>(P, c, e);
 }
 
+// flush_finish in two groups (k_round_ps): first the near deliveries, as
+// flush_finish makes them -- every inbox or remote one, every calendar one
+// whose claim overflowed, and every calendar one into a bin before far_b, the
+// first bin no receiver reads before the barrier after next (the caller's
+// rule) -- then the far ones, the same stores under the other predicate.
+// When the wave has a far lane the far group is exactly kFarVm vector-memory
+// instructions, the wave's youngest (ev_st_sc1's two stores and the bitmap's
+// atomic without return), so `s_waitcnt vmcnt(kFarVm)` drains everything
+// before it and leaves it in flight (ps_publish); `any` says whether it was
+// issued.  A far delivery is not noted (far_b is not before pf_lim).  The
+// lane's far delivery time, or kInf
+constexpr uint32_t kFarVm = 3;
+template <bool XCH = true>
+__device__ __forceinline__ uint64_t flush_finish_far(const DParams& P, HostCtx& c, const PendDel& pd, uint64_t far_b,
+                                                     bool& any) {
+    const shd_event e = s_res[threadIdx.x];
+    const bool far = pd.kind == 1 && pd.slot < kBinCap && !pd.near && (e.time >> P.bin_shift) >= far_b;
+    if (pd.kind != 0 && !far) {
+        if (pd.kind == 1 && pd.slot < kBinCap) {
+            ev_st_sc1(&P.bins[pd.bi * kBinCap + pd.slot], e);
+            const uint32_t p = (uint32_t)(pd.bi & (kNB - 1));
+            const int32_t dl = (int32_t)e.dst - P.h0;
+            atomicOr(&P.bin_bits[(size_t)dl * kNBW + (p >> 5)], 1u << (p & 31));
+            if (pd.near) note_dirty(dl);
+        } else {
+            emit_nocal<XCH>(P, c, e);
+        }
+    }
+    any = __ballot(far) != 0;
+    if (any) {   // (wave-uniform: inside, the far lanes' mask is not empty and the three instructions issue)
+        if (far) {
+            ev_st_sc1(&P.bins[pd.bi * kBinCap + pd.slot], e);
+            const uint32_t p = (uint32_t)(pd.bi & (kNB - 1));
+            const int32_t dl = (int32_t)e.dst - P.h0;
+            atomicOr(&P.bin_bits[(size_t)dl * kNBW + (p >> 5)], 1u << (p & 31));
+        }
+    }
+    return far ? e.time : kInf;
+}
+
 // The steps of flush_wave on their own, for the two-step last flush below (which
 // takes one record per lane).  The walk: each host walks its own sends in send order
 // (worker.c:286-320): event IDs, counters, traces, first-touch logs; s_res

@@ -1325,11 +1325,34 @@ struct PsNoFin {
 // pass in which no lane runs an event, and a wave without an active lane
 // does not enter the loop.  steady_iter takes the carried candidate in place
 // of its own minimum.
-template <bool PF, bool XCH = true, class Fin = PsNoFin, bool STEADY = false, bool EXIT = false>
+//
+// CARRY (k_round_ps; PF): the last flush's far deliveries complete behind the
+// share.  The block's next time N -- the wave's least `next` and min_emit, and
+// the bound carried from the previous round's far deliveries (cy->carry): the
+// value its share publishes -- is folded before the stores (under the claims'
+// round trip) and comes back in `next`, wave-uniform.  Every block's N is at
+// least the gather's fold, so the next window ends at or before lim = min(N +
+// window, stop), and before the barrier after next a receiver reads no bin
+// from b(lim) + kPfBins on: not this round's prefetch (pf_lim is not behind
+// it), not the next window, not the next round's prefetch.  The deliveries
+// into those bins are issued last (flush_finish_far) and ps_publish leaves
+// them in flight; the next round's share drains them, being younger.  The
+// bitmap a receiver loads at the next round's start may so miss a far
+// delivery's bit, which stands for the bin's start in that round's next time:
+// the sender publishes it in its place (cy->far_t, folded by the caller into
+// the next round's cy->carry).
+struct PsCarry {
+    uint64_t window, stop;
+    uint64_t carry;   // in: the earliest bin start of the previous round's far deliveries (kInf: none)
+    uint64_t far_t;   // out: the lane's far delivery time (kInf: none)
+    bool any;         // out: the wave issued a far group
+};
+template <bool PF, bool XCH = true, class Fin = PsNoFin, bool STEADY = false, bool EXIT = false, bool CARRY = false>
 __device__ __forceinline__ void ps_loop_close(const DParams& P, HostCtx& c, bool active, bool has, const PsRsrc& R,
                                               uint32_t lb, uint64_t we, uint32_t (&w)[kNBW], uint32_t clr_p,
                                               uint32_t clr, uint64_t& next, PfBins* pb, uint64_t* span,
-                                              const Fin& fin = Fin{}) {
+                                              const Fin& fin = Fin{}, PsCarry* cy = nullptr) {
+    static_assert(PF || !CARRY, "the far group is the two-step last flush's");
     PendDel pd;
     pd.kind = 0;
     uint32_t total = 0;   // the sends of a last flush of one batch
@@ -1471,7 +1494,7 @@ __device__ __forceinline__ void ps_loop_close(const DParams& P, HostCtx& c, bool
 #else
         TIMVP(8, t_take);    // in take_next + begin_event (+ the fused notification / refill)
 #endif
-#ifndef SHD_TIMING_EXIT
+#if !defined(SHD_TIMING_EXIT) && !defined(SHD_TIMING_CARRY)   // (SHD_TIMING_CARRY, a NOLOOP build: slot 9 is the last flush's kinds)
         TIMVP(9, t_work);    // in run_work
 #endif
         TIMVP(10, t_fl);     // in the flushes before the last
@@ -1524,12 +1547,37 @@ __device__ __forceinline__ void ps_loop_close(const DParams& P, HostCtx& c, bool
         loop_done();
         // the stores wait for the calendar claims alone; a delivery into a
         // bin loaded ahead is noted here
-        flush_finish<XCH>(P, c, pd);
+        if (CARRY) {
+            if (active && c.min_emit < next) next = c.min_emit;
+            uint64_t n = wave_min_u64(next);
+            n = cy->carry < n ? cy->carry : n;
+            next = n;
+            uint64_t lim = n + cy->window;
+            if (lim > cy->stop || lim < n) lim = cy->stop;
+            cy->far_t = flush_finish_far<XCH>(P, c, pd, (lim >> P.bin_shift) + kPfBins, cy->any);
+#ifdef SHD_TIMING_CARRY   // 1 + (the last flush had a near delivery) + 2 x (a far one)
+            TIMVP(9, 1ull + (__ballot(pd.kind != 0 && cy->far_t == kInf) != 0 ? 1u : 0u) + (cy->any ? 2u : 0u));
+#endif
+        } else {
+#ifdef SHD_TIMING_CARRY   // the same under the rule, for a build without it (k_round_ps: cy is given)
+            if (cy) {
+                uint64_t n = next;
+                if (active && c.min_emit < n) n = c.min_emit;
+                n = wave_min_u64(n);
+                uint64_t lim = n + cy->window;
+                if (lim > cy->stop || lim < n) lim = cy->stop;
+                const bool far = pd.kind == 1 && pd.slot < kBinCap && !pd.near &&
+                                 (s_res[threadIdx.x].time >> P.bin_shift) >= (lim >> P.bin_shift) + kPfBins;
+                TIMVP(9, 1ull + (__ballot(pd.kind != 0 && !far) != 0 ? 1u : 0u) + (__ballot(far) != 0 ? 2u : 0u));
+            }
+#endif
+            flush_finish<XCH>(P, c, pd);
+        }
 #ifdef SHD_TIMING_LIGHT
         TIMP(21);   // the claims are back, the last flush's stores issued (k_round_sp: 20, 21 are its own)
 #endif
     }
-    if (active && c.min_emit < next) next = c.min_emit;
+    if (!CARRY && active && c.min_emit < next) next = c.min_emit;
     TIMP(5);
 }
 
@@ -1554,11 +1602,31 @@ __device__ __forceinline__ uint32_t ps_goff(uint32_t nsl, uint32_t slot, uint32_
 __device__ __forceinline__ uint32_t ps_goff(uint32_t nsl, uint32_t slot, uint32_t g) { return (g * nsl + slot) * 16u; }
 #endif
 // the share of round i: its three granules tagged, stored write-through after
-// the wave's hand-off stores drained; d: the noted destinations
+// the wave's hand-off stores drained; d: the noted destinations.
+// CARRY and `far` (wave-uniform): the wave's kFarVm youngest vector-memory
+// instructions are its far group (flush_finish_far), which stays in flight:
+// vector-memory operations complete in issue order, so everything older has
+// landed, and an instruction issued behind the group only makes the wait
+// longer.  The next share's wait takes the group in, being older than it
+template <bool CARRY = false>
 __device__ __forceinline__ void ps_publish(__amdgpu_buffer_rsrc_t rs, uint32_t nsl, uint32_t slot, uint64_t next,
                                            uint32_t flags, uint32_t nev, uint32_t npkt, uint32_t nact, uint32_t tag,
-                                           uint4 d) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every store of this wave has landed
+                                           uint4 d, bool far = false) {
+    static_assert(kFarVm == 3, "the waits below name the far group's size");
+#if defined(SHD_TIMING_LIGHT) && defined(SHD_TIMING_NOWAIT)
+    // the timing build's stamps between the far group and here are stores of their own, issued by
+    // every block below 2048 (stamps 21 and 5, and slot 9 of a SHD_TIMING_CARRY build): counted in,
+    // so that the stamps show the product's wait
+#ifdef SHD_TIMING_CARRY
+    if (CARRY && far && blockIdx.x < 2048) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+#else
+    if (CARRY && far && blockIdx.x < 2048) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
+#endif
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#else
+    if (CARRY && far) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");   // every store before the far group has landed
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every store of this wave has landed
+#endif
     if (threadIdx.x == 0) {
         st16_sc1(rs, ps_goff(nsl, slot, 0), make_uint4((uint32_t)next, (uint32_t)(next >> 32), flags, tag));
         st16_sc1(rs, ps_goff(nsl, slot, 1), make_uint4(nev, npkt, nact, tag));
@@ -1731,6 +1799,13 @@ constexpr bool kPsDueAhead = true;
 #else
 constexpr bool kPsDueAhead = false;
 #endif
+// the last flush's far deliveries complete behind the share (ps_loop_close's
+// CARRY); SHD_NO_CARRY builds the round without it, for an A/B
+#ifndef SHD_NO_CARRY
+constexpr bool kPsCarry = kPsPf;
+#else
+constexpr bool kPsCarry = false;
+#endif
 
 template <bool LEAN>
 __global__ __launch_bounds__(kBlock) void k_round_ps(uint64_t window, int nb, DevSummary* __restrict__ ring,
@@ -1780,6 +1855,7 @@ __global__ __launch_bounds__(kBlock) void k_round_ps(uint64_t window, int nb, De
     uint32_t pnd = 0, dirty = 0;
     uint64_t pspan = 0;
     PfDue pdu{0, kInf, kInf};   // LEAN && kPsDueAhead: what pf_stage knows of the next window's due list
+    PsCarry cy{window, stop, kInf, kInf, false};   // kPsCarry: the far deliveries' bound, from a round to the next
     for (int i = 0; i < nb; i++) {
         PS_PARAMS(i);
         const unsigned long long t_start = wall_clock64();
@@ -1838,16 +1914,20 @@ __global__ __launch_bounds__(kBlock) void k_round_ps(uint64_t window, int nb, De
             nev = wave_sum_u32(c.c_events);
             npkt = wave_sum_u32(c.c_pkt);
         };
-        ps_loop_close<kPsPf, false, decltype(fin), LEAN && kPsSteady, LEAN && kPsSteady && kPsExit>(
-            P, c, active, has, R, lb, we, w, (uint32_t)(ws >> P.bin_shift) & (kNB - 1), clr, next, &pb, &span, fin);
+        ps_loop_close<kPsPf, false, decltype(fin), LEAN && kPsSteady, LEAN && kPsSteady && kPsExit, kPsCarry>(
+            P, c, active, has, R, lb, we, w, (uint32_t)(ws >> P.bin_shift) & (kNB - 1), clr, next, &pb, &span, fin, &cy);
         acc[2] += c.c_sent; acc[3] += c.c_idrop;
         const uint32_t pend = c.n_pend ? kPsPend : 0u;
         const uint32_t fl = wave_or_u32(c.err | pend);
-        next = wave_min_u64(next);
+        if (!kPsCarry) next = wave_min_u64(next);   // (kPsCarry: folded ahead of the stores)
         const uint32_t tag = tag0 + (uint32_t)i;
         const uint32_t base = (uint32_t)(i & 1) * nblk;
-        ps_publish(rs, 2 * nblk, base + blockIdx.x, next, fl, nev, npkt, nact, tag, ps_noted(pfm));
+        ps_publish<kPsCarry>(rs, 2 * nblk, base + blockIdx.x, next, fl, nev, npkt, nact, tag, ps_noted(pfm), cy.any);
         TIMP(6);
+        if (kPsCarry) {   // the far deliveries' bound for the next share, folded behind this one
+            const uint64_t t = wave_min_u64(cy.far_t);
+            cy.carry = t == kInf ? kInf : (t >> P.bin_shift) << P.bin_shift;
+        }
         if (pfm) {   // the next window's events, staged while the other blocks finish
             const uint64_t b1 = we >> P.bin_shift;
             // every staged event before lim is the next round's: its window ends at
