@@ -505,6 +505,9 @@ typedef struct shd_run_stats {
                                        was ambiguous (shd_eng_run_until) */
     uint64_t n_restore_points;      /* restore points renewed between the batches of this call
                                        (a point older than 2^16 rounds) */
+    uint64_t n_batches_fused;       /* shd_xgroup batches launched on the fused peer-to-peer
+                                       schedule (k_round_px / k_round_spx; the first round of a
+                                       k_round_px batch is a k_round_xtl); shd_eng: 0 */
 } shd_run_stats;
 
 typedef struct shd_eng shd_eng;

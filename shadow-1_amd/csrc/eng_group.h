@@ -883,9 +883,11 @@ extern "C" int shd_xgroup_run_until(shd_xgroup* g, uint64_t t_stop, shd_run_stat
             SHD_HIP(hipMemsetAsync(e->d_halt, 0, 4, e->stream));
         }
         SHD_HIP(hipEventRecord(g->engs[0]->bev[0], g->engs[0]->stream));
-        const bool sparse_batch = g->fused && x_sparse(g);
+        const bool fused_batch = g->fused;   // (as launched: the spill recovery below may leave the schedule)
+        const bool sparse_batch = fused_batch && x_sparse(g);
         if ((rc = x_launch_rounds(g, nb))) break;
         s.n_batches++;
+        if (fused_batch) s.n_batches_fused++;
         if (sparse_batch) s.n_batches_sparse++;
         g->xepoch += (uint64_t)nb;
         SHD_HIP(hipGetLastError());

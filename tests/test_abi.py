@@ -99,13 +99,16 @@ def test_model_struct_layout_matches_the_header(tmp_path):
                    'int main(void){printf("%%zu %%zu %%zu %%zu %%zu %%zu %%zu\\n", sizeof(shd_model),'
                    ' offsetof(shd_model, app_peer), offsetof(shd_model, app_spec), offsetof(shd_model, host_app),'
                    ' offsetof(shd_model, n_app_specs), sizeof(shd_udp_app), sizeof(shd_run_stats));'
-                   'printf("%%zu\\n", offsetof(shd_run_stats, n_rounds_replayed));return 0;}\n' % REPO)
+                   'printf("%%zu %%zu\\n", offsetof(shd_run_stats, n_rounds_replayed),'
+                   ' offsetof(shd_run_stats, n_batches_fused));return 0;}\n' % REPO)
     exe = tmp_path / "m"
     subprocess.run(["gcc", str(src), "-o", str(exe)], check=True)
     got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
     assert got == [C.sizeof(S.Model), S.Model.app_peer.offset, S.Model.app_spec.offset, S.Model.host_app.offset,
                    S.Model.n_app_specs.offset, C.sizeof(S.UdpApp), C.sizeof(S.RunStats),
-                   S.RunStats.n_rounds_replayed.offset]
+                   S.RunStats.n_rounds_replayed.offset, S.RunStats.n_batches_fused.offset]
+    # n_batches_fused is appended: the last field, after n_restore_points
+    assert S.RunStats.n_batches_fused.offset == S.RunStats.n_restore_points.offset + 8 == got[6] - 8
 
 
 def test_pc_info_layout_matches_the_header(tmp_path):
