@@ -379,7 +379,12 @@ enum { SHD_QF_NO_CALENDAR = 1,
        /* with `trace`: also the application's side of each datagram
         * (SHD_TR_CREATED, SHD_TR_READ), for the [STATUS] packet lines
         * (packet_addDeliveryStatus, packet.c:647-659; shdgpu.status_lines) */
-       SHD_QF_TRACE_STATUS = 16 };
+       SHD_QF_TRACE_STATUS = 16,
+       /* keep one shd_tcp_hostrec (shdtcp.h) per local host: what its router
+        * queue and its interface did, counted on the device where the reference
+        * raises the packet statuses, in an untraced run as well (read with
+        * shd_eng_host_records) */
+       SHD_QF_HOST_RECORDS = 32 };
 
 /* one event (32 B): key (time, dst, src, seq) = event_compare, event.c:110-153 */
 typedef struct shd_event {
@@ -627,6 +632,22 @@ int shd_eng_stream(shd_eng* e, void** hip_stream);
  * differences give the [shadow-heartbeat] [node] line (tracker.c:419-465).
  * *n = nloc*K*2; SHD_ERANGE if cap < *n. */
 int shd_eng_heartbeats(shd_eng* e, uint32_t* out, uint64_t cap, uint64_t* n);
+/* host records (model queue_flags & SHD_QF_HOST_RECORDS; SHD_EINVAL without):
+ * out[i] = the record of host host_begin + i, with the fields and the count
+ * points of shd_tcp_hostrec (shdtcp.h; tests/tcp_host_expect.py) -- every
+ * count is a number of [STATUS] lines of a traced run that the host executed:
+ * ROUTER_ENQUEUED / _DEQUEUED / _DROPPED at its upstream router queue (an
+ * arrival that meets an empty queue and a token is one enqueue and one dequeue
+ * of sojourn 0), RCV_INTERFACE_RECEIVED / _DROPPED (the loopback delivery
+ * included) and SND_INTERFACE_SENT (packets to the host's own address
+ * included); bytes are shd_model.payload per packet; tcp_throttled and
+ * tcp_unordered stay 0.  `host` is the model's host index.  Callable after
+ * any run call, any number of times: it reads the records and resets nothing;
+ * a rolled-back or replayed round counts once.  In a group every engine holds
+ * its own hosts' records: the ranks' arrays in rank order are the one-engine
+ * array.  *n = host_end - host_begin; SHD_ERANGE if cap < *n. */
+struct shd_tcp_hostrec;
+int shd_eng_host_records(shd_eng* e, struct shd_tcp_hostrec* out, uint64_t cap, uint64_t* n);
 
 /* ---- the reference's log lines, made by the library ----
  * A set of lines: line i is text[off[i] .. off[i+1]) (no newline; text is

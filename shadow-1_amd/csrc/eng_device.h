@@ -228,7 +228,8 @@ static_assert(sizeof(DestGuide) == 48, "guide entry: three 16-B loads");
 constexpr int kDestExc = 16;   // closed-form destination exceptions (ParamsT::exc_x)
 // ParamsT::feat: the model's optional features (all off on the bench's models)
 constexpr uint32_t F_TRACE = 1u, F_HB = 2u, F_PCOUNT = 4u, F_HOSTHB = 8u, F_AMBIG = 16u, F_STATUS = 64u,
-                   F_APP = 128u;    // the application is not PHOLD: per-host modes (app_send / app_dest)
+                   F_APP = 128u,    // the application is not PHOLD: per-host modes (app_send / app_dest)
+                   F_HOSTREC = 32u; // SHD_QF_HOST_RECORDS: per-host router-queue / interface records (ParamsT::hrec)
 
 template <template <class> class Ptr>
 struct ParamsT {
@@ -334,6 +335,10 @@ struct ParamsT {
     uint32_t xnbx;                     // region blocks per rank: ceil(ceil(H / xworld) / hpw)
     uint32_t xrcap;                    // region slots used: min(kXSlots, xcap) (small blocks force spills)
     uint64_t xroff;                    // events from a rank's receive base to its regions
+    // host records (SHD_QF_HOST_RECORDS: F_HOSTREC), else null: one per local
+    // host, written by the host's own lane alone (hrec_count).  Last, so that every
+    // other field keeps its place in the kernels' argument block
+    Ptr<shd_tcp_hostrec> hrec;         // [nloc]
 };
 // The host fills Params (plain pointers); device code reads the same bytes
 // as DParams, whose pointers carry the global address space, so that loads
@@ -698,6 +703,63 @@ __device__ __forceinline__ void trace(const DParams& P, HostCtx& c, uint64_t t, 
 
 __device__ __forceinline__ bool bootstrapping(const DParams& P, const HostCtx& c) { return c.now < c.k.boot_end; }
 
+// ---- host records (SHD_QF_HOST_RECORDS; shd_tcp_hostrec, shdtcp.h) ----
+// The count points are the reference's packet statuses on the executing host
+// (router.c:113, 129, router_queue_codel.c:139; network_interface.c:382, 411,
+// 545), as on the TCP path (tcp.hip host_status).  The host's lane is its
+// record's only writer, and nobody reads the record during a run: plain loads
+// and stores into HBM, nothing in the host context.  Every count point tests
+// F_HOSTREC first (HotK::feat, an SGPR: a scalar branch), so a model without
+// the flag skips the loads, and the LEAN instantiations (feat = 0 at compile
+// time) hold none of this.  The count points lie on the general paths only:
+// with the flag, begin_event's straight-line arrivals, its straight-to-the-wire
+// loop and notify_fast step aside, as they do for F_TRACE, and the packet takes
+// router_enqueue / codel_dequeue / if_send_step, which compute the same.  Every
+// datagram of a model carries shd_model.payload bytes (the line's bytes=), so
+// the byte fields are count x payload: they, depth_end and host are filled in
+// by shd_eng_host_records.
+enum : uint32_t { HR_ENQUEUED, HR_DEQUEUED, HR_DROPPED, HR_IF_RECEIVED, HR_IF_DROPPED, HR_IF_SENT };
+// one status on the record `r` at `now`; arg: HR_ENQUEUED the queue's length
+// right after, this packet included; HR_DEQUEUED the packet's enqueue time.
+// One body for all the count points, called: inlined at each of them it is a
+// few hundred instructions more in kernels that have no registers to spare.
+__device__ __noinline__ void hrec_count(GlobalPtr<shd_tcp_hostrec> r, uint64_t now, uint32_t what, uint64_t arg) {
+    if (!r->t_first) r->t_first = now;
+    r->t_last = now;
+    switch (what) {
+    case HR_ENQUEUED:   // ROUTER_ENQUEUED (router.c:113)
+        r->router_enqueued++;
+        if ((uint32_t)arg > r->depth_max) { r->depth_max = (uint32_t)arg; r->t_depth_max = now; }
+        break;
+    case HR_DEQUEUED: {   // ROUTER_DEQUEUED (router.c:129)
+        const uint64_t so = now - arg;
+        r->sojourn_sum += so;
+        if (so > r->sojourn_max || r->router_dequeued == 0) { r->sojourn_max = so; r->t_sojourn_max = now; }
+        r->router_dequeued++;
+        const uint64_t hi = so >> 16;   // bucket min(15, bit_length(sojourn >> 16))
+        const uint32_t b = hi ? 64u - (uint32_t)__clzll((long long)hi) : 0u;
+        r->sojourn_hist[b < 15u ? b : 15u]++;
+        break;
+    }
+    case HR_DROPPED: r->router_dropped++; break;     // ROUTER_DROPPED (router_queue_codel.c:139)
+    case HR_IF_RECEIVED: r->if_received++; break;    // RCV_INTERFACE_RECEIVED (network_interface.c:382)
+    case HR_IF_DROPPED: r->if_dropped++; break;      // RCV_INTERFACE_DROPPED (:411)
+    default: r->if_sent++; break;                    // HR_IF_SENT: SND_INTERFACE_SENT (:545)
+    }
+}
+// HR: the count points are compiled in (the default).  The event functions
+// that hold one, or that step aside for one, carry HR as a template parameter,
+// and the LEAN kernels instantiate them with HR = false: their text is then the
+// text without count points, so those kernels compile to what they were (the
+// count points folded away behind feat = 0 as well, but only after inlining,
+// and the code objects differed in their scalar spills).
+template <bool HR>
+__device__ __forceinline__ bool hrec_on(const HostCtx& c) { return HR && (c.k.feat & F_HOSTREC) != 0; }
+template <bool HR>
+__device__ __forceinline__ void hrec(const DParams& P, const HostCtx& c, uint32_t what, uint64_t arg = 0) {
+    if (HR && (c.k.feat & F_HOSTREC)) hrec_count(P.hrec + c.l, c.now, what, arg);
+}
+
 // the tracker interval of host h (<host heartbeatfrequency>, host.c:240; the
 // option default otherwise)
 __device__ __forceinline__ uint64_t hb_interval(const DParams& P, uint32_t feat, uint32_t h) {
@@ -877,8 +939,10 @@ __device__ __forceinline__ void rq_push(const DParams& P, HostCtx& c, uint32_t s
 }
 
 // _networkinterface_receivePacket (network_interface.c:375-419)
+template <bool HR = true>
 __device__ void if_receive_packet(const DParams& P, HostCtx& c, uint32_t src, uint32_t pkt) {
     c.if_in++;   // tracker_addInputBytes (network_interface.c:415)
+    hrec<HR>(P, c, (c.flags & F_LISTENING) ? HR_IF_RECEIVED : HR_IF_DROPPED);
     if (c.flags & F_LISTENING) {
         trace(P, c, c.now, 0, c.h, src, pkt, SHD_TR_RECV);
         c.c_recv++;
@@ -923,11 +987,14 @@ __device__ bool codel_helper(const DParams& P, HostCtx& c, bool& okToDrop, Codel
     return true;
 }
 
+template <bool HR = true>
 __device__ __forceinline__ void codel_drop(const DParams& P, HostCtx& c, const CodelEnt& e) {
     trace(P, c, c.now, 0, c.h, e.src, e.pkt, SHD_TR_CODEL_DROP);
+    hrec<HR>(P, c, HR_DROPPED);
     c.c_cdrop++;
 }
 
+template <bool HR = true>
 __device__ bool codel_dequeue(const DParams& P, HostCtx& c, CodelEnt& out) {
     bool okToDrop = false;
     CodelEnt pkt;
@@ -936,14 +1003,14 @@ __device__ bool codel_dequeue(const DParams& P, HostCtx& c, CodelEnt& out) {
     if (c.flags & F_CODEL_DROP_MODE) {
         if (!okToDrop) c.flags &= ~F_CODEL_DROP_MODE;
         while (c.now >= c.cq_ndrop && (c.flags & F_CODEL_DROP_MODE)) {
-            codel_drop(P, c, pkt);
+            codel_drop<HR>(P, c, pkt);
             c.cq_dc++;
             have = codel_helper(P, c, okToDrop, pkt);
             if (okToDrop) c.cq_ndrop = codel_control_law(c.cq_dc, c.cq_ndrop);
             else c.flags &= ~F_CODEL_DROP_MODE;
         }
     } else if (okToDrop) {
-        codel_drop(P, c, pkt);
+        codel_drop<HR>(P, c, pkt);
         have = codel_helper(P, c, okToDrop, pkt);
         c.flags |= F_CODEL_DROP_MODE;
         const uint32_t delta = c.cq_dc - c.cq_dcl;
@@ -954,17 +1021,19 @@ __device__ bool codel_dequeue(const DParams& P, HostCtx& c, CodelEnt& out) {
         c.cq_dcl = c.cq_dc;
     }
     if (!have) return false;
+    hrec<HR>(P, c, HR_DEQUEUED, pkt.ts);   // router_dequeue's ROUTER_DEQUEUED (router.c:129): the packet CoDel hands out
     out = pkt;
     return true;
 }
 
 // networkinterface_receivePackets (network_interface.c:421-455)
+template <bool HR = true>
 __device__ void if_receive_packets(const DParams& P, HostCtx& c) {
     const bool boot = bootstrapping(P, c);
     while (boot || c.rx_rem >= SHD_MTU) {
         CodelEnt p;
-        if (!codel_dequeue(P, c, p)) break;
-        if_receive_packet(P, c, p.src, p.pkt);
+        if (!codel_dequeue<HR>(P, c, p)) break;
+        if_receive_packet<HR>(P, c, p.src, p.pkt);
         if (!boot) {
             consume(c.rx_rem, c.k.pkt_len);
             refill_if_needed(P, c);
@@ -1661,6 +1730,7 @@ __device__ __forceinline__ void flush_last_consume(const DParams& P, HostCtx& c,
 // Returns true when it stopped early for a flush of the deferred sends (the
 // buffer is full, or the next send is a loopback, whose trace and event take
 // the exact event ID); the caller flushes and calls it again.
+template <bool HR = true>
 __device__ bool if_send_step(const DParams& P, HostCtx& c) {
     const bool boot = bootstrapping(P, c);
     while (c.tx_rem >= SHD_MTU) {
@@ -1679,6 +1749,7 @@ __device__ bool if_send_step(const DParams& P, HostCtx& c) {
         c.tq_hv = false;
         c.tq_head = (c.tq_head + 1 == c.k.tq_cap) ? 0 : c.tq_head + 1;
         c.tq_count--;
+        hrec<HR>(P, c, HR_IF_SENT);   // SND_INTERFACE_SENT (network_interface.c:545), loopback included
         if (self) {
             trace(P, c, c.now, c.ev_seq, c.h, c.h, p.pkt, SHD_TR_LOCAL);
             c.if_out++;
@@ -1799,14 +1870,15 @@ __device__ bool enqueue_new_message(const DParams& P, HostCtx& c) {
 }
 
 // _networkinterface_refillTokenBucketsCB (network_interface.c:163-183)
+template <bool HR = true>
 __device__ void refill_cb(const DParams& P, HostCtx& c) {
     c.flags &= ~F_REFILL_PENDING;
     c.rx_rem += c.rx_refill;
     if (c.rx_rem > c.rx_refill + SHD_MTU) c.rx_rem = c.rx_refill + SHD_MTU;
     c.tx_rem += c.tx_refill;
     if (c.tx_rem > c.tx_refill + SHD_MTU) c.tx_rem = c.tx_refill + SHD_MTU;
-    if_receive_packets(P, c);
-    if (if_send_step(P, c)) c.err |= SHD_ERR_INTERNAL;   // boot: nothing queued, nothing deferred
+    if_receive_packets<HR>(P, c);
+    if (if_send_step<HR>(P, c)) c.err |= SHD_ERR_INTERNAL;   // boot: nothing queued, nothing deferred
     refill_if_needed(P, c);
 }
 
@@ -1826,9 +1898,10 @@ __device__ void refill_cb(const DParams& P, HostCtx& c) {
 // buffer, past the bootstrap period: one new message, sent at once unless it
 // draws this host (then the general send loop takes it).  The same draws and
 // steps, in the same order, as the general NOTIFY path of begin_event.
+template <bool HR = true>
 __device__ __forceinline__ bool notify_fast_ok(const DParams& P, const HostCtx& c) {
     return c.unread == 1u && c.tq_count == 0 && c.tx_rem >= SHD_MTU && send_room() &&
-           !(c.k.feat & F_TRACE) && !bootstrapping(P, c);
+           !(c.k.feat & F_TRACE) && !bootstrapping(P, c) && !hrec_on<HR>(c);
 }
 // (room: send_room(), read by the caller)
 __device__ __forceinline__ bool notify_fast_ok_room(const DParams& P, const HostCtx& c, bool room) {
@@ -1873,6 +1946,7 @@ __device__ __forceinline__ void refill_fast(const DParams& P, HostCtx& c) {
     refill_if_needed(P, c);
 }
 
+template <bool HR = true>
 __device__ void begin_event(const DParams& P, HostCtx& c, const shd_event& e) {
     TCNT(5);
     c.c_events++;
@@ -1889,9 +1963,11 @@ __device__ void begin_event(const DParams& P, HostCtx& c, const shd_event& e) {
     // epoll notification is scheduled at +1 ns unless one is pending (its ID
     // is consumed even when it falls past the end).  The same steps as the
     // general path below, in the same order.  (arrival_fast_ok / arrival_fast
-    // below restate this test and body for steady_iter: change both together.)
+    // below restate this test and body for steady_iter: change both together --
+    // but for hrec_on: host records take the general path here, as tracing
+    // does, and steady_iter runs in LEAN kernels only, which have none.)
     if (e.kind == SHD_EV_PACKET && c.cq_count == 0 && c.rx_rem >= SHD_MTU && (c.flags & F_LISTENING) &&
-        !(c.k.feat & F_TRACE) && !bootstrapping(P, c)) {
+        !(c.k.feat & F_TRACE) && !bootstrapping(P, c) && !hrec_on<HR>(c)) {
         c.c_pkt++;
         c.c_recv++;
         c.if_in++;
@@ -1911,7 +1987,7 @@ __device__ void begin_event(const DParams& P, HostCtx& c, const shd_event& e) {
         refill_if_needed(P, c);
         return;
     }
-    if (e.kind == SHD_EV_NOTIFY && notify_fast_ok(P, c)) {
+    if (e.kind == SHD_EV_NOTIFY && notify_fast_ok<HR>(P, c)) {
         notify_fast(P, c);
         return;
     }
@@ -1959,14 +2035,14 @@ __device__ void begin_event(const DParams& P, HostCtx& c, const shd_event& e) {
         // _worker_runDeliverPacketTask -> router_enqueue (router.c:104-122)
         c.c_pkt++;
         trace(P, c, c.now, e.seq, c.h, e.src, e.pkt, SHD_TR_ARRIVE);
-        if (c.cq_count == 0 && c.rx_rem >= SHD_MTU && !bootstrapping(P, c)) {
+        if (c.cq_count == 0 && c.rx_rem >= SHD_MTU && !bootstrapping(P, c) && !hrec_on<HR>(c)) {
             // an empty router queue and room in the receive bucket: the packet
             // is enqueued and dequeued at once (sojourn 0: CoDel's interval
             // and drop mode reset; the second dequeue attempt finds nothing)
             c.cq_head = (c.cq_head + 1 == c.k.cq_cap) ? 0 : c.cq_head + 1;
             c.cq_iexp = 0;
             c.flags &= ~F_CODEL_DROP_MODE;
-            if_receive_packet(P, c, e.src, e.pkt);
+            if_receive_packet<HR>(P, c, e.src, e.pkt);
             consume(c.rx_rem, c.k.pkt_len);
             refill_if_needed(P, c);
             break;
@@ -1984,11 +2060,12 @@ __device__ void begin_event(const DParams& P, HostCtx& c, const shd_event& e) {
         }
         c.cq_count++;
         c.cq_total += c.k.pkt_len;
+        hrec<HR>(P, c, HR_ENQUEUED, c.cq_count);
         c.w_fl = was_empty ? W_RX : 0u;
         break;
     }
     case SHD_EV_LOCAL:
-        if_receive_packet(P, c, c.h, e.pkt);
+        if_receive_packet<HR>(P, c, c.h, e.pkt);
         break;
     case SHD_EV_NOTIFY:
         c.flags &= ~F_NOTIFY_PENDING;
@@ -2001,14 +2078,14 @@ __device__ void begin_event(const DParams& P, HostCtx& c, const shd_event& e) {
         break;
     }
     if (c.w_fl & W_RX) {
-        if_receive_packets(P, c);
+        if_receive_packets<HR>(P, c);
         c.w_fl &= ~W_RX;
     }
     // new messages while the send queue is empty and the bucket has room go
     // straight to the wire (enqueue, then the send loop pops it at once);
     // anything else -- a loopback, a full send buffer, a backlog, the
     // bootstrap period -- is left to run_work's general loop, in order
-    const bool boot = bootstrapping(P, c);
+    const bool boot = bootstrapping(P, c) || hrec_on<HR>(c);   // (with host records: the general send loop counts)
     // (one exit: a loopback ends the loop through tq_count)
     while (c.w_msgs && c.tq_count == 0 && c.tx_rem >= SHD_MTU && send_room() && !boot) {
         app_read(P, c);
@@ -2032,10 +2109,11 @@ __device__ void begin_event(const DParams& P, HostCtx& c, const shd_event& e) {
 
 // the event's shared steps: while (msgs || tx) { a new message if any;
 // the send loop }; then the refill check.  False when it stopped for a flush.
+template <bool HR = true>
 __device__ bool run_work(const DParams& P, HostCtx& c) {
     for (;;) {
         if (c.w_fl & W_SENDING) {
-            if (if_send_step(P, c)) return false;
+            if (if_send_step<HR>(P, c)) return false;
             c.w_fl &= ~W_SENDING;
         }
         if (c.w_msgs) {

@@ -425,7 +425,7 @@ __device__ __forceinline__ void round_body(const DParams& P, const HostIn& in, u
                     if (more) {
                         c.now = e.time;
                         KT0(q1)
-                        begin_event(P, c, e);
+                        begin_event<!LEAN>(P, c, e);
                         KTA(k_be, q1)
 #if defined(SHD_TIMING) && !defined(SHD_TIMING_LIGHT)
                         i_be = clock64();
@@ -441,7 +441,7 @@ __device__ __forceinline__ void round_body(const DParams& P, const HostIn& in, u
                         // spreading them over two iterations)
                         if (st == 0u && c.tt2 < we) {
                             const uint64_t t = c.tt2, ht = c.evq_n ? c.top_time : kInf;
-                            if (t < c.tt0 && t < c.tt1 && t < c.dt && t < ht && notify_fast_ok(P, c)) {
+                            if (t < c.tt0 && t < c.tt1 && t < c.dt && t < ht && notify_fast_ok<!LEAN>(P, c)) {
                                 TCNT(5);
                                 c.tt2 = kInf;
                                 c.now = t;
@@ -473,7 +473,7 @@ __device__ __forceinline__ void round_body(const DParams& P, const HostIn& in, u
                 }
                 if (st == 1u) {
                     KT0(q2)
-                    st = run_work(P, c) ? 0u : 2u;
+                    st = run_work<!LEAN>(P, c) ? 0u : 2u;
                     KTA(k_rw, q2)
                 }
 #if defined(SHD_TIMING) && !defined(SHD_TIMING_LIGHT)
@@ -1347,7 +1347,9 @@ struct PsCarry {
     uint64_t far_t;   // out: the lane's far delivery time (kInf: none)
     bool any;         // out: the wave issued a far group
 };
-template <bool PF, bool XCH = true, class Fin = PsNoFin, bool STEADY = false, bool EXIT = false, bool CARRY = false>
+// HR (eng_device.h): false in the LEAN kernels.
+template <bool PF, bool XCH = true, class Fin = PsNoFin, bool STEADY = false, bool EXIT = false, bool CARRY = false,
+          bool HR = true>
 __device__ __forceinline__ void ps_loop_close(const DParams& P, HostCtx& c, bool active, bool has, const PsRsrc& R,
                                               uint32_t lb, uint64_t we, uint32_t (&w)[kNBW], uint32_t clr_p,
                                               uint32_t clr, uint64_t& next, PfBins* pb, uint64_t* span,
@@ -1400,7 +1402,7 @@ __device__ __forceinline__ void ps_loop_close(const DParams& P, HostCtx& c, bool
 #endif
                     if (got) {
                         c.now = e.time;
-                        begin_event(P, c, e);
+                        begin_event<HR>(P, c, e);
 #ifdef SHD_TIMING_INLOOP
                         t_q[1] += wall_clock64() - q1;
 #endif
@@ -1411,7 +1413,7 @@ __device__ __forceinline__ void ps_loop_close(const DParams& P, HostCtx& c, bool
 #endif
                         if (st == 0u && c.tt2 < we) {   // the notification, when it is next (round_body)
                             const uint64_t t = c.tt2, ht = c.evq_n ? c.top_time : kInf;
-                            if (t < c.tt0 && t < c.tt1 && t < c.dt && t < ht && notify_fast_ok(P, c)) {
+                            if (t < c.tt0 && t < c.tt1 && t < c.dt && t < ht && notify_fast_ok<HR>(P, c)) {
                                 c.tt2 = kInf; c.now = t; c.c_events++;
                                 c.q_seq = c.ts2; c.q_src = c.h; c.q_sub = 0;
                                 c.w_msgs = 0; c.w_fl = 0;
@@ -1443,7 +1445,7 @@ __device__ __forceinline__ void ps_loop_close(const DParams& P, HostCtx& c, bool
                     ta = tb;
                 }
 #endif
-                if (st == 1u) st = run_work(P, c) ? 0u : 2u;
+                if (st == 1u) st = run_work<HR>(P, c) ? 0u : 2u;
 #ifdef SHD_TIMING_INLOOP
                 t_work += wall_clock64() - ta;
 #endif
@@ -1582,13 +1584,14 @@ __device__ __forceinline__ void ps_loop_close(const DParams& P, HostCtx& c, bool
 }
 
 // k_round_sp's round of an active host (ps_prologue + ps_loop_close)
-template <bool SP, bool XCH = true>
+template <bool SP, bool XCH = true, bool HR = true>
 __device__ __forceinline__ void ps_round_body(const DParams& P, HostCtx& c, bool active, uint32_t lb, const PsRsrc& R,
                                               uint64_t ws, uint64_t we, int parity, uint32_t nin,
                                               uint32_t (&w)[kNBW], uint32_t wbits, uint64_t& next,
                                               const SpIn* sp = nullptr) {
     ps_prologue<SP>(P, c, active, lb, R, ws, we, parity, nin, w, wbits, sp);
-    ps_loop_close<false, XCH>(P, c, active, active, R, lb, we, w, 0u, 0u, next, nullptr, nullptr);
+    ps_loop_close<false, XCH, PsNoFin, false, false, false, HR>(P, c, active, active, R, lb, we, w, 0u, 0u, next, nullptr,
+                                                                nullptr);
 }
 
 // The shares' granules are stored in three planes (round 6): granule g of slot
@@ -1914,7 +1917,7 @@ __global__ __launch_bounds__(kBlock) void k_round_ps(uint64_t window, int nb, De
             nev = wave_sum_u32(c.c_events);
             npkt = wave_sum_u32(c.c_pkt);
         };
-        ps_loop_close<kPsPf, false, decltype(fin), LEAN && kPsSteady, LEAN && kPsSteady && kPsExit, kPsCarry>(
+        ps_loop_close<kPsPf, false, decltype(fin), LEAN && kPsSteady, LEAN && kPsSteady && kPsExit, kPsCarry, !LEAN>(
             P, c, active, has, R, lb, we, w, (uint32_t)(ws >> P.bin_shift) & (kNB - 1), clr, next, &pb, &span, fin, &cy);
         acc[2] += c.c_sent; acc[3] += c.c_idrop;
         const uint32_t pend = c.n_pend ? kPsPend : 0u;
@@ -2129,7 +2132,7 @@ __device__ __forceinline__ void sp_scan(const DParams& P, const PsRsrc& R, uint3
 // lane's share (PEND: a logged first touch flags kPsPend)
 // (alist: the scan's list; lrec / lhn: the block's hosts' records and next
 // times in LDS, or null: the global ones)
-template <bool PEND, bool XCH = true>
+template <bool PEND, bool XCH = true, bool HR = true>
 __device__ __forceinline__ void sp_passes(const DParams& P, HostCtx& c, const PsRsrc& R, uint32_t hb, uint32_t nact,
                                           uint64_t ws, uint64_t we, int parity, uint32_t xwi, uint64_t& next,
                                           uint32_t& nev, uint32_t& npkt, uint32_t& fl, uint32_t& nhost,
@@ -2166,7 +2169,7 @@ __device__ __forceinline__ void sp_passes(const DParams& P, HostCtx& c, const Ps
         }
         const uint32_t wbits = ps_window_bits(P, c, w, ws, we);
         uint64_t hn = kInf;
-        ps_round_body<true, XCH>(P, c, act, lb, R, ws, we, parity, nin, w, wbits, hn, &in);
+        ps_round_body<true, XCH, HR>(P, c, act, lb, R, ws, we, parity, nin, w, wbits, hn, &in);
         if (act) {
             if (lrec) store_ctx(P, c, &lrec[lb], &lhn[lb]);
             else store_ctx(P, c);
@@ -2253,7 +2256,7 @@ __global__ __launch_bounds__(kBlock) void k_round_sp(uint64_t window, int nb, De
         TIMVP(21, (uint64_t)((nact + kBlock - 1) / kBlock));   // passes
         // the active hosts, 64 at a time
         uint32_t nev = 0, npkt = 0, fl = 0, nhost = 0;
-        sp_passes<true, false>(P, c, R, hb, nact, ws, we, parity, 0u, next, nev, npkt, fl, nhost, alist, lrec, lhn);
+        sp_passes<true, false, !LEAN>(P, c, R, hb, nact, ws, we, parity, 0u, next, nev, npkt, fl, nhost, alist, lrec, lhn);
         next = wave_min_u64(next);
         nev = wave_sum_u32(nev);
         npkt = wave_sum_u32(npkt);

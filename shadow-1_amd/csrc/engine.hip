@@ -44,6 +44,7 @@
 #include <vector>
 
 #include "shd_device.h"
+#include "../../include/shdtcp.h"   // shd_tcp_hostrec: the packet engine's host records use the TCP path's type
 
 namespace {
 
@@ -599,7 +600,14 @@ extern "C" int shd_eng_create(const shd_model* m, shd_pc* pc, int32_t host_begin
         int rc;
         if (k && (rc = ealloc(e, &P.hb, (size_t)n * k))) { shd_eng_destroy(e); return rc; }
     }
-    P.feat = (m->trace ? F_TRACE : 0u) | (P.hb ? F_HB : 0u) | (P.pcount ? F_PCOUNT : 0u) |
+    if (m->queue_flags & SHD_QF_HOST_RECORDS) {
+        // one record per local host, zeroed; on the allocation list, so a
+        // protected round's state copy, its rollback and run_until's restore
+        // point carry it: a round that runs twice counts once
+        int rc;
+        if ((rc = ealloc(e, &P.hrec, (size_t)n))) { shd_eng_destroy(e); return rc; }
+    }
+    P.feat = (m->trace ? F_TRACE : 0u) | (P.hb ? F_HB : 0u) | (P.pcount ? F_PCOUNT : 0u) | (P.hrec ? F_HOSTREC : 0u) |
              (P.host_hb ? F_HOSTHB : 0u) | (P.force_ambig ? F_AMBIG : 0u) |
              ((m->trace && (m->queue_flags & SHD_QF_TRACE_STATUS)) ? F_STATUS : 0u) |
              (P.app != SHD_APP_PHOLD ? F_APP : 0u);
@@ -1712,6 +1720,33 @@ extern "C" int shd_eng_heartbeats(shd_eng* e, uint32_t* out, uint64_t cap, uint6
     SHD_HIP(hipSetDevice(e->device));
     SHD_HIP(hipMemcpyAsync(out, (const uint2*)e->P.hb, 4 * cnt, hipMemcpyDeviceToHost, e->stream));
     SHD_HIP(hipStreamSynchronize(e->stream));
+    return SHD_OK;
+}
+
+extern "C" int shd_eng_host_records(shd_eng* e, shd_tcp_hostrec* out, uint64_t cap, uint64_t* n) {
+    if (!e || !n || (cap && !out)) return SHD_EINVAL;
+    if (!e->P.hrec) return SHD_EINVAL;   // SHD_QF_HOST_RECORDS was not set
+    const uint64_t cnt = (uint64_t)e->nloc;
+    *n = cnt;
+    if (cap < cnt) return SHD_ERANGE;
+    if (!cnt) return SHD_OK;
+    SHD_HIP(hipSetDevice(e->device));
+    SHD_HIP(hipMemcpyAsync(out, e->P.hrec, sizeof(shd_tcp_hostrec) * cnt, hipMemcpyDeviceToHost, e->stream));
+    SHD_HIP(hipStreamSynchronize(e->stream));
+    // what the device does not keep: the host index, what the queue still
+    // holds, and the byte counts -- every datagram of the model carries
+    // `payload` bytes (the [STATUS] line's bytes=)
+    const uint64_t payload = e->P.payload;
+    for (uint64_t i = 0; i < cnt; i++) {
+        shd_tcp_hostrec& r = out[i];
+        r.host = (int32_t)(e->P.h0 + (int32_t)i);
+        r.depth_end = (uint32_t)(r.router_enqueued - r.router_dequeued - r.router_dropped);
+        r.router_enqueued_bytes = r.router_enqueued * payload;
+        r.router_dequeued_bytes = r.router_dequeued * payload;
+        r.router_dropped_bytes = r.router_dropped * payload;
+        r.if_received_bytes = r.if_received * payload;
+        r.if_sent_bytes = r.if_sent * payload;
+    }
     return SHD_OK;
 }
 

@@ -25,6 +25,7 @@ SHD_QF_COUNT_PATHS = 2      # queue_flags: per-path packet counters on the devic
 SHD_QF_HEARTBEATS = 4       # queue_flags: tracker node counters at every heartbeat
 SHD_QF_NO_APP_START = 8     # queue_flags: the caller pushes the application starts (shd_eng_push_events)
 SHD_QF_TRACE_STATUS = 16    # queue_flags: with trace, the application's records too (status_lines)
+SHD_QF_HOST_RECORDS = 32    # queue_flags: one TcpHostRec per host from the packet engine (Engine.host_records)
 ERR_AMBIGUOUS = 16          # shd_round_summary.error: an ambiguous first-touch drop decision (SHD_ERR_AMBIGUOUS)
 SHD_PHOLD_LISTEN_PORT = 8998   # PHOLD_LISTEN_PORT, test_phold.c:34
 SHD_MIN_RANDOM_PORT = 10000    # MIN_RANDOM_PORT, definitions.h:94
@@ -424,6 +425,7 @@ _SIGS = {
     "shd_eng_digest": (C.c_int, [C.c_void_p, C.c_void_p]),
     "shd_eng_path_counts": (C.c_int, [C.c_void_p, P(C.c_uint64), C.c_uint64, P(C.c_uint64)]),
     "shd_eng_heartbeats": (C.c_int, [C.c_void_p, P(C.c_uint32), C.c_uint64, P(C.c_uint64)]),
+    "shd_eng_host_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, P(C.c_uint64)]),
     "shd_eng_stream": (C.c_int, [C.c_void_p, P(C.c_void_p)]),
     "shd_status_lines": (C.c_int, [C.c_void_p, C.c_uint64, P(C.c_uint32), P(C.c_uint32), C.c_uint32, C.c_uint32,
                                    C.c_uint32, P(C.c_int32), P(P(Lines))]),
@@ -677,7 +679,8 @@ HOSTS_CSV_FIELDS = tuple(k for k in TCP_HOSTREC_DTYPE.names if k not in ("_pad",
 
 def write_hosts_csv(path, recs) -> int:
     """Write host records (TCP_HOSTREC_DTYPE, as tcp.run(..., hosts=True)
-    returns them) as CSV: a header line (HOSTS_CSV_FIELDS), then one line per
+    returns them, or sim.Engine.host_records() of a packet-engine model with
+    SHD_QF_HOST_RECORDS: the same records, written unchanged) as CSV: a header line (HOSTS_CSV_FIELDS), then one line per
     host in the records' order; times and sojourns in ns, bucket k of the
     histogram in column sojourn_hist_k.  Returns the number of rows."""
     a = np.asarray(recs, dtype=TCP_HOSTREC_DTYPE)

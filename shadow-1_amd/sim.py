@@ -232,6 +232,19 @@ class Engine:
         nloc = self.h1 - self.h0
         return out.reshape(nloc, (n.value // (2 * nloc)) if nloc else 0, 2)
 
+    def host_records(self) -> np.ndarray:
+        """One S.TCP_HOSTREC_DTYPE record per local host (SHD_QF_HOST_RECORDS in the
+        model's queue_flags; shd_eng_host_records): what the host's router queue
+        and interface did so far, from an untraced run as well.  Record i is host
+        h0 + i; the call reads the records and resets nothing.  The type is the
+        TCP path's, so S.write_hosts_csv writes the array and S.merge_tcp_hosts
+        joins a group's ranks unchanged."""
+        n = C.c_uint64()
+        out = np.zeros(self.h1 - self.h0, dtype=S.TCP_HOSTREC_DTYPE)
+        S.check(S.lib().shd_eng_host_records(self.ptr, out.ctypes.data if len(out) else None, len(out),
+                                             C.byref(n)), "shd_eng_host_records")
+        return out[:n.value]
+
     def status_lines(self, ips, host_ids=None, listen_port=S.SHD_PHOLD_LISTEN_PORT) -> list:
         """[(time_ns, host, line)]: the [STATUS] lines of the engine's trace, made
         by the library (shd_eng_status_lines, packet.c:647-659)"""
