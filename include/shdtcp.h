@@ -348,9 +348,16 @@ typedef struct shd_tcp_result {
  * ends (state: 0 CLOSED, 1 LISTEN, 2 SYNSENT, 3 SYNRECEIVED, 4 ESTABLISHED,
  * 5 FINWAIT1, 6 FINWAIT2, 7 CLOSING, 8 TIMEWAIT, 9 CLOSEWAIT, 10 LASTACK, the
  * order of tcp.c's enum TCPState; cwnd and ssthresh in segments; srtt and
- * rttvar in ms).  Nothing
- * the reference build prints pins these five: they are the device's own and
- * the tests check only that they do not depend on tracing or the path mode. */
+ * rttvar in ms).  They are
+ * what the reference's tcp_getInfo exports as tcpi_state, tcpi_snd_cwnd,
+ * tcpi_snd_ssthresh, tcpi_rtt and tcpi_rttvar (tcp.c:1409-1459).  The pin has
+ * two links: the oracle's values equal the reference's wherever a process can
+ * observe its socket -- each time it runs, from the socket's creation until
+ * the process closes it (tests/test_tcp_snapshots_ref_cpu.py) -- and the
+ * records equal the oracle's change log at the end of the run
+ * (tests/test_tcp_snapshots_gpu.py).  What follows the close (the FIN
+ * exchange, TIMEWAIT, CLOSED) no reference process observes: it is pinned
+ * oracle-to-device only. */
 typedef struct shd_tcp_flow {
     int32_t host, proc;               /* the model's host index; process index      */
     uint32_t local_ip, peer_ip;
@@ -369,8 +376,9 @@ typedef struct shd_tcp_flow {
  * (shd_tcp_result_flows' index) as it stood at boundary t -- the seven
  * counters of shd_tcp_flow, pinned by a traced run's [STATUS] lines
  * (tests/tcp_series_expect.py), and the socket's state, cwnd, ssthresh, srtt
- * and rttvar when the sample was taken (by the host's first event at or past
- * t, or at the end of the run), which are the device's own as in shd_tcp_flow. */
+ * and rttvar when the sample was taken (before the host's first event at or
+ * past t, or at the end of the run): the oracle's change log just before t,
+ * pinned as shd_tcp_flow's five are (tests/test_tcp_snapshots_gpu.py). */
 typedef struct shd_tcp_sample {
     uint64_t t;                 /* the boundary T_k, ns */
     uint32_t flow;              /* index into shd_tcp_result_flows' array of the same result */

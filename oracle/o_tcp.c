@@ -356,6 +356,10 @@ typedef struct osock {
     /* server / child (tcp.c:91-113) */
     int server; ivec children; ivec pending; uint32_t last_peer_ip, last_ip; uint16_t last_peer_port;
     int child; int32_t parent; int child_state;
+    /* cfg->snapshots: serial: the socket's number in creation order; desc: the
+     * host's descriptor table holds it (host_lookupDescriptor resolves its
+     * handle); snap: its last row of the change log (snap_any: it has one) */
+    uint32_t serial; int desc, snap_any; int64_t snap[5];
 } osock;
 
 typedef struct oproc {
@@ -396,6 +400,9 @@ typedef struct {
     int32_t active;                      /* the executing event's host (-1 after a deliver task) */
     opkt** pool; uint32_t npool, cappool; /* packets by CoDel id */
     obuf out;
+    uint32_t next_serial;
+    int64_t* obs; uint64_t n_obs, cap_obs;
+    int64_t* log; uint64_t n_log, cap_log;
 } T;
 
 static T* G;
@@ -528,6 +535,55 @@ static void tcp_process(osock* k, opkt* p);
 static void udp_release(osock* k);
 
 static int32_t sidx(const osock* k) { return (int32_t)(k - G->s); }
+
+/* ------------------------------------------------------------ snapshots
+ * (o_tcp_out.obs / .log; only with cfg->snapshots) */
+static int64_t* snap_row(int64_t** a, uint64_t* n, uint64_t* cap, uint32_t cols) {
+    if (*n == *cap) { *cap = *cap ? 2 * *cap : 256; *a = realloc(*a, *cap * cols * sizeof(int64_t)); }
+    return *a + (*n)++ * cols;
+}
+/* socket_getSocketName / socket_getPeerName (socket.c:168-223), 0 where unset;
+ * tcp_getInfo's five (tcp.c:1409-1459) */
+static void snap_fill(const osock* k, int64_t* addr, int64_t* five) {
+    addr[0] = addr[1] = addr[2] = addr[3] = 0;
+    if (k->bound) {
+        addr[0] = (k->bound_ip == 0 && k->peer_ip == 0x7f000001u) ? 0x7f000001u : k->bound_ip;
+        addr[1] = k->bound_port;
+    }
+    if (k->peer_ip != 0 && k->peer_port != 0) { addr[2] = k->peer_ip; addr[3] = k->peer_port; }
+    five[0] = k->state; five[1] = k->cwnd; five[2] = k->reno.ssthresh;
+    five[3] = (uint32_t)k->timing.srtt; five[4] = (uint32_t)k->timing.rttvar;
+}
+static void snap_observe_sock(const oproc* pr, int32_t si) {
+    if (si < 0) return;
+    const osock* k = &G->s[si];
+    if (!k->used || k->udp || !k->desc) return;
+    int64_t* r = snap_row(&G->obs, &G->n_obs, &G->cap_obs, O_TCP_OBS_COLS);
+    r[0] = (int64_t)G->now; r[1] = pr->host; r[2] = pr->index;
+    snap_fill(k, r + 3, r + 7);
+    r[12] = k->serial;
+}
+static void snap_observe(const oproc* pr) {
+    if (!G->cfg->snapshots) return;
+    snap_observe_sock(pr, pr->fd);
+    snap_observe_sock(pr, pr->listenfd);
+}
+/* after an event of host h: only that host's sockets can have changed */
+static void snap_log(int32_t h) {
+    for (uint32_t i = 0; i < G->ns; i++) {
+        osock* k = &G->s[i];
+        if (!k->used || k->udp || k->host != h) continue;
+        int64_t addr[4], five[5];
+        snap_fill(k, addr, five);
+        if (k->snap_any && !memcmp(five, k->snap, sizeof(five))) continue;
+        k->snap_any = 1;
+        memcpy(k->snap, five, sizeof(five));
+        int64_t* r = snap_row(&G->log, &G->n_log, &G->cap_log, O_TCP_LOG_COLS);
+        r[0] = (int64_t)G->now; r[1] = h; r[2] = k->serial;
+        memcpy(r + 3, addr, sizeof(addr));
+        memcpy(r + 7, five, sizeof(five));
+    }
+}
 
 /* ------------------------------------------------------------ epoll (epoll.c)
  * The process's one watch: its readiness (_epollwatch_isReady: not closed,
@@ -799,6 +855,8 @@ static int32_t sock_new(int32_t h) {   /* tcp_new (tcp.c:2452-2512) */
     osock* k = &G->s[si];
     memset(k, 0, sizeof(*k));
     k->used = 1;
+    k->serial = G->next_serial++;
+    k->desc = 1;
     k->host = h;
     k->handle = G->h[h].next_handle++;
     k->proc = -1;
@@ -1050,7 +1108,7 @@ static void tcp_flush(osock* k) {   /* tcp.c:1121-1278 */
 }
 
 /* _host_disassociateInterface via host_closeDescriptor */
-static void host_close_descriptor(osock* k) { k->assoc = 0; k->assoc_general = 0; }
+static void host_close_descriptor(osock* k) { k->assoc = 0; k->assoc_general = 0; k->desc = 0; }
 
 static void tcp_set_state(osock* k, int st) {   /* tcp.c:607-693 */
     k->state_last = k->state;
@@ -1624,6 +1682,7 @@ static void app_wait(oproc* pr, int32_t fd, uint32_t events) {   /* epoll_ctl AD
 static void app_run(oproc* pr) {
     const int32_t h = pr->host;
     const uint32_t N = G->cfg->tcp_bytes;
+    snap_observe(pr);
     for (;;) {
         switch (pr->step) {
         case T_SRV_START: {
@@ -1668,7 +1727,7 @@ static void app_run(oproc* pr) {
                 pr->done += (uint32_t)n;
             }
             if (pr->step == T_SRV_RECV) { pr->done = 0; pr->step = T_SRV_SEND; }
-            else { tcp_close(&G->s[pr->fd]); pr->step = T_DONE; }
+            else { snap_observe(pr); tcp_close(&G->s[pr->fd]); pr->step = T_DONE; }
             break;
         }
         case T_SRV_SEND:
@@ -1681,7 +1740,9 @@ static void app_run(oproc* pr) {
                 pr->done += (uint32_t)n;
             }
             if (pr->step == T_SRV_SEND) {
+                snap_observe(pr);
                 tcp_close(&G->s[pr->fd]);
+                snap_observe(pr);
                 tcp_close(&G->s[pr->listenfd]);
                 pr->step = T_DONE;
             } else {
@@ -1702,6 +1763,7 @@ static void app_run(oproc* pr) {
             const uint32_t ip = G->h[sp->host].ip;
             const uint16_t port = G->s[sp->listenfd].bound_port;
             const int rc = host_connect(h, &G->s[pr->fd], ip, port);
+            snap_observe(pr);
             if (rc == ERR_EINPROGRESS || rc == ERR_EALREADY) { app_wait(pr, pr->fd, 4); return; }
             if (rc != 0 && rc != ERR_EISCONN) { pr->step = T_DONE; return; }
             pr->done = 0;
@@ -1966,6 +2028,11 @@ int o_tcp_run(const o_tcp_cfg* cfg, o_topo* topo, o_tcp_out* out) {
         t.now = e.time;
         execute(&e);
         out->events++;
+        if (cfg->snapshots) snap_log((int32_t)e.dst);
+    }
+    if (cfg->snapshots) {   /* (a caller without the flag may hold the struct as it ended at `events`) */
+        out->obs = t.obs; out->n_obs = t.n_obs;
+        out->log = t.log; out->n_log = t.n_log;
     }
     out->lines = t.out.s;
     out->len = t.out.len;
@@ -2001,5 +2068,16 @@ void o_tcp_free(o_tcp_out* out) {
     free(out->next_event_id);
     free(out->next_packet_id);
     free(out->rng_probe);
-    memset(out, 0, sizeof(*out));
+    out->lines = NULL; out->len = 0; out->n_lines = 0;
+    out->next_event_id = out->next_packet_id = NULL; out->rng_probe = NULL;
+    out->events = 0;
+}
+
+/* a run with cfg->snapshots: its obs and log, before o_tcp_free */
+void o_tcp_free_snapshots(o_tcp_out* out) {
+    if (!out) return;
+    free(out->obs);
+    free(out->log);
+    out->obs = out->log = NULL;
+    out->n_obs = out->n_log = 0;
 }

@@ -230,7 +230,9 @@ typedef struct o_tcp_cfg {
     /* datagram processes beside the echo ones (shdtcp.h's shd_tcp_model fields) */
     const int32_t* proc_app;          /* [P] -1 echo, else the application's index; NULL: none */
     const uint32_t* app_spec;         /* [n][4] {send, dest, n_start, per_read} */
-    uint32_t udp_payload, _pad;
+    uint32_t udp_payload;
+    uint32_t snapshots;               /* 1: fill o_tcp_out.obs and .log, freed with o_tcp_free_snapshots (off: nothing
+                                         is recorded and nothing of o_tcp_out past `events` is touched) */
     const int32_t* app_peer;          /* [H] */
     const double* dest_cum;           /* [n_classes][H] */
     const uint8_t* host_class;        /* [H] or NULL */
@@ -240,9 +242,29 @@ typedef struct o_tcp_out {
     char* lines; size_t len; uint64_t n_lines;
     uint64_t* next_event_id; uint64_t* next_packet_id; uint32_t* rng_probe;
     uint64_t events;                  /* events executed */
+    /* cfg->snapshots: a TCP socket's state (tcp.c's enum TCPState order), cwnd,
+     * reno.ssthresh, timing.srtt, timing.rttvar -- what tcp_getInfo exports as
+     * tcpi_state, tcpi_snd_cwnd, tcpi_snd_ssthresh, tcpi_rtt, tcpi_rttvar.
+     * obs: the sockets an echo process holds (its socket, then its listener;
+     * those the host's descriptor table still holds), each time the process
+     * runs until it blocks, after its connect call and before each of its closes, as
+     * oracle/ref_harness/ref_loop.c observes the reference -- O_TCP_OBS_COLS
+     * int64 per row: time, host, process, local ip, local port, peer ip, peer
+     * port (socket_getSocketName / socket_getPeerName; 0: unset), the five
+     * values, the socket's serial number.
+     * log: after every executed event, a row for every TCP socket of the
+     * event's host whose five values differ from its last row (its first row:
+     * the event that created it) -- O_TCP_LOG_COLS int64 per row: the event's
+     * time, host, the socket's serial number, the same addresses as they stand
+     * after the event, the five values. */
+    int64_t* obs; uint64_t n_obs;
+    int64_t* log; uint64_t n_log;
 } o_tcp_out;
+#define O_TCP_OBS_COLS 13
+#define O_TCP_LOG_COLS 12
 int o_tcp_run(const o_tcp_cfg* cfg, o_topo* topo, o_tcp_out* out);
 void o_tcp_free(o_tcp_out* out);
+void o_tcp_free_snapshots(o_tcp_out* out);   /* obs and log of a run with cfg->snapshots */
 
 #ifdef __cplusplus
 }

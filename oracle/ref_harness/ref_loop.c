@@ -45,7 +45,9 @@
 #include <glib.h>
 #include <glib/gstdio.h>
 #include <netinet/in.h>
+#include <netinet/tcp.h>
 #include <stdarg.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -65,6 +67,7 @@
 #include "main/core/worker.h"
 #include "main/host/descriptor/descriptor.h"
 #include "main/host/descriptor/socket.h"
+#include "main/host/descriptor/tcp.h"
 #include "main/host/host.h"
 #include "main/host/process.h"
 #include "main/routing/address.h"
@@ -100,7 +103,11 @@ typedef struct ref_loop_cfg {
     /* app 1 (TCP echo): proc_peer[k] = -1 for a server, else the server process
      * the client k connects to; each client sends tcp_bytes, the server echoes */
     const int32_t* proc_peer;
-    uint32_t tcp_bytes, _pad3;
+    uint32_t tcp_bytes;
+    /* 1: fill ref_loop_out.obs (the caller's ref_loop_out has the fields from
+     * obs on, and frees them with ref_loop_free_obs); 0: the struct ends before
+     * obs and nothing past it is touched */
+    uint32_t observe;
     /* 1: the default log level's work only -- debug records filtered (the
      * [STATUS] lines are not even formatted) and no line kept: for timing the
      * reference's loop (scripts/r04/ref_loop_timing.py) */
@@ -132,7 +139,15 @@ typedef struct ref_loop_out {
     uint64_t* next_packet_id;     /* [H] */
     uint32_t* rng_probe;          /* [H] random_rand of the host RNG at the end */
     double mark_wall_s[2];        /* monotonic seconds at mark_time[k] (0 if never reached) */
+    /* app 1: what tcp_getInfo (tcp.c, getsockopt(TCP_INFO)'s source) gives for
+     * the TCP descriptors an echo process holds, each time the process runs,
+     * after its connect call and before each of its closes -- REF_OBS_COLS int64 per row: time, host,
+     * process, local ip, local port, peer ip, peer port (host byte order, 0:
+     * unset), tcpi_state, tcpi_snd_cwnd, tcpi_snd_ssthresh, tcpi_rtt, tcpi_rttvar */
+    int64_t* obs;
+    uint64_t n_obs, cap_obs;
 } ref_loop_out;
+#define REF_OBS_COLS 12
 
 static const ref_loop_cfg* g_cfg;
 static ref_loop_out* g_out;
@@ -586,9 +601,44 @@ static int tcp_server_port(int32_t spi, in_addr_t* ip, in_port_t* port) {
     return 0;
 }
 
+/* one row of ref_loop_out.obs per TCP descriptor the process holds (its
+ * socket, then its listener) that the host's table still resolves: tcp_getInfo
+ * only reads */
+static void tcp_observe_fd(Process* proc, gint fd) {
+    if (fd < 0 || !g_out || !g_cfg->observe) return;
+    Descriptor* d = host_lookupDescriptor(proc->host, fd);
+    if (!d || descriptor_getType(d) != DT_TCPSOCKET) return;
+    struct tcp_info ti;
+    tcp_getInfo((TCP*)d, &ti);
+    in_addr_t lip = 0, pip = 0;
+    in_port_t lport = 0, pport = 0;
+    (void)socket_getSocketName((Socket*)d, &lip, &lport);
+    (void)socket_getPeerName((Socket*)d, &pip, &pport);
+    if (g_out->n_obs == g_out->cap_obs) {
+        g_out->cap_obs = g_out->cap_obs ? 2 * g_out->cap_obs : 256;
+        g_out->obs = realloc(g_out->obs, g_out->cap_obs * REF_OBS_COLS * sizeof(int64_t));
+    }
+    int64_t* r = g_out->obs + g_out->n_obs++ * REF_OBS_COLS;
+    r[0] = (int64_t)worker_getCurrentTime();
+    r[1] = host_index_of(host_getID(proc->host));
+    r[2] = proc->index;
+    r[3] = ntohl(lip); r[4] = ntohs(lport); r[5] = ntohl(pip); r[6] = ntohs(pport);
+    r[7] = ti.tcpi_state; r[8] = ti.tcpi_snd_cwnd; r[9] = ti.tcpi_snd_ssthresh;
+    r[10] = ti.tcpi_rtt; r[11] = ti.tcpi_rttvar;
+}
+static void tcp_observe(Process* proc) {
+    tcp_observe_fd(proc, proc->fd);
+    tcp_observe_fd(proc, proc->listenfd);
+}
+static gint tcp_close_observed(Process* proc, gint fd) {
+    tcp_observe(proc);
+    return host_closeUser(proc->host, fd);
+}
+
 static void tcp_run(Process* proc) {
     Host* host = proc->host;
     const uint32_t N = g_cfg->tcp_bytes;
+    tcp_observe(proc);
     for (;;) {
         switch (proc->step) {
         case T_SRV_START: {
@@ -632,7 +682,7 @@ static void tcp_run(Process* proc) {
                 proc->done = 0;
                 proc->step = T_SRV_SEND;
             } else {
-                (void)host_closeUser(host, proc->fd);
+                (void)tcp_close_observed(proc, proc->fd);
                 proc->step = T_DONE;
             }
             break;
@@ -647,8 +697,8 @@ static void tcp_run(Process* proc) {
                 proc->done += (guint32)n;
             }
             if (proc->step == T_SRV_SEND) {
-                (void)host_closeUser(host, proc->fd);
-                (void)host_closeUser(host, proc->listenfd);
+                (void)tcp_close_observed(proc, proc->fd);
+                (void)tcp_close_observed(proc, proc->listenfd);
                 proc->step = T_DONE;
             } else {
                 proc->done = 0;
@@ -674,6 +724,7 @@ static void tcp_run(Process* proc) {
                 return;
             }
             gint rc = host_connectToPeer(host, proc->fd, (struct sockaddr*)&a);
+            tcp_observe(proc);   /* the one point where a process sees its socket before the handshake ends */
             if (rc == EINPROGRESS || rc == EALREADY) { tcp_wait(proc, proc->fd, EPOLLOUT); return; }
             if (rc != 0 && rc != EISCONN) { proc->step = T_DONE; return; }
             proc->done = 0;
@@ -755,7 +806,7 @@ int ref_loop_run(const ref_loop_cfg* cfg, ref_loop_out* out) {
     if (!cfg || !out || cfg->n_hosts <= 0 || !cfg->path) return -1;
     g_cfg = cfg;
     g_out = out;
-    memset(out, 0, sizeof(*out));
+    memset(out, 0, cfg->observe ? sizeof(*out) : offsetof(ref_loop_out, obs));
     const int32_t H = cfg->n_hosts;
     out->ip = calloc((size_t)H, sizeof(uint32_t));
     out->next_event_id = calloc((size_t)H, sizeof(uint64_t));
@@ -840,5 +891,13 @@ void ref_loop_free(ref_loop_out* out) {
     free(out->next_event_id);
     free(out->next_packet_id);
     free(out->rng_probe);
-    memset(out, 0, sizeof(*out));
+    memset(out, 0, offsetof(ref_loop_out, obs));
+}
+
+/* a run with cfg->observe: its observation rows, before ref_loop_free */
+void ref_loop_free_obs(ref_loop_out* out) {
+    if (!out) return;
+    free(out->obs);
+    out->obs = NULL;
+    out->n_obs = out->cap_obs = 0;
 }

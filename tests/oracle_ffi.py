@@ -332,7 +332,7 @@ class TcpCfg(C.Structure):
                 ("tcp_bytes", C.c_uint32), ("recv_buf", C.c_uint32), ("send_buf", C.c_uint32),
                 ("tcp_window", C.c_uint32), ("no_lines", C.c_uint32), ("qdisc_rr", C.c_uint32),
                 ("proc_app", C.POINTER(C.c_int32)), ("app_spec", C.POINTER(C.c_uint32)),
-                ("udp_payload", C.c_uint32), ("_pad", C.c_uint32), ("app_peer", C.POINTER(C.c_int32)),
+                ("udp_payload", C.c_uint32), ("snapshots", C.c_uint32), ("app_peer", C.POINTER(C.c_int32)),
                 ("dest_cum", C.POINTER(C.c_double)), ("host_class", C.POINTER(C.c_uint8)),
                 ("n_classes", C.c_int32), ("_pad2", C.c_int32)]
 
@@ -340,17 +340,28 @@ class TcpCfg(C.Structure):
 class TcpOut(C.Structure):
     _fields_ = [("lines", C.c_char_p), ("len", C.c_size_t), ("n_lines", C.c_uint64),
                 ("next_event_id", C.POINTER(C.c_uint64)), ("next_packet_id", C.POINTER(C.c_uint64)),
-                ("rng_probe", C.POINTER(C.c_uint32)), ("events", C.c_uint64)]
+                ("rng_probe", C.POINTER(C.c_uint32)), ("events", C.c_uint64),
+                ("obs", C.POINTER(C.c_int64)), ("n_obs", C.c_uint64),
+                ("log", C.POINTER(C.c_int64)), ("n_log", C.c_uint64)]
+
+
+# o_tcp_out.obs / .log (oracle.h): the five values tcp_getInfo exports, where
+# the reference's harness observes them and after every event that changed them
+TCP_OBS_FIELDS = ("t", "host", "proc", "local_ip", "local_port", "peer_ip", "peer_port",
+                  "state", "cwnd", "ssthresh", "srtt", "rttvar", "sock")
+TCP_LOG_FIELDS = ("t", "host", "sock", "local_ip", "local_port", "peer_ip", "peer_port",
+                  "state", "cwnd", "ssthresh", "srtt", "rttvar")
 
 
 def tcp_run(model, g, ips, procs, peers, nbytes=20000, recv_buf=174760, send_buf=131072, tcp_window=10,
-            lines=True, qdisc=0, udp=None):
+            lines=True, qdisc=0, udp=None, snapshots=False):
     """The oracle's TCP echo run (o_tcp.c) on the model's hosts: procs = [(host,
     start)], peers = [-1 | server process]; ips: host-order uint32 per host.
     Returns dict(lines=[(t, h, line)], next_event_id, next_packet_id, rng_probe)
     with a delivery copy's release (host -1) put on its receiver, as the
     reference-loop binding does.  udp: as shadow-1_amd/tcp.py's (datagram
-    processes beside the echo ones)."""
+    processes beside the echo ones).  snapshots: also obs and log, lists of int
+    rows per TCP_OBS_FIELDS / TCP_LOG_FIELDS (oracle.h o_tcp_out)."""
     import numpy as np
     m = model.struct
     H = int(m.n_hosts)
@@ -381,6 +392,7 @@ def tcp_run(model, g, ips, procs, peers, nbytes=20000, recv_buf=174760, send_buf
     cfg.tcp_window = tcp_window
     cfg.no_lines = 0 if lines else 1
     cfg.qdisc_rr = int(qdisc)
+    cfg.snapshots = 1 if snapshots else 0
     if udp is not None:
         pa = np.ascontiguousarray(udp["apps"], dtype=np.int32)
         sp = np.ascontiguousarray([[int(x) for x in a] for a in udp["specs"]], dtype=np.uint32).ravel()
@@ -414,6 +426,12 @@ def tcp_run(model, g, ips, procs, peers, nbytes=20000, recv_buf=174760, send_buf
                    next_packet_id=np.ctypeslib.as_array(out.next_packet_id, shape=(H,)).copy(),
                    rng_probe=np.ctypeslib.as_array(out.rng_probe, shape=(H,)).copy(),
                    events=int(out.events))
+        if snapshots:
+            for key, n, ptr, cols in (("obs", out.n_obs, out.obs, len(TCP_OBS_FIELDS)),
+                                      ("log", out.n_log, out.log, len(TCP_LOG_FIELDS))):
+                res[key] = np.ctypeslib.as_array(ptr, shape=(int(n), cols)).tolist() if n else []
+            l.o_tcp_free_snapshots.argtypes = [C.POINTER(TcpOut)]
+            l.o_tcp_free_snapshots(C.byref(out))
         l.o_tcp_free(C.byref(out))
     finally:
         lib().o_topo_free(topo)

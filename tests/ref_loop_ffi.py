@@ -35,7 +35,7 @@ class Cfg(C.Structure):
                 ("heartbeat_interval", C.c_uint64), ("app_start", C.c_uint64),
                 ("load", C.c_uint32), ("payload", C.c_uint32),
                 ("path", C.c_void_p), ("path_ctx", C.c_void_p), ("root_dir", C.c_char_p),
-                ("proc_peer", P(C.c_int32)), ("tcp_bytes", C.c_uint32), ("_pad3", C.c_uint32),
+                ("proc_peer", P(C.c_int32)), ("tcp_bytes", C.c_uint32), ("observe", C.c_uint32),
                 ("quiet", C.c_int32), ("qdisc_rr", C.c_int32), ("mark_time", C.c_uint64 * 2),
                 ("app_spec", P(C.c_uint32)), ("host_app", P(C.c_uint8)), ("app_peer", P(C.c_int32)),
                 ("proc_app", P(C.c_int32))]
@@ -44,14 +44,37 @@ class Cfg(C.Structure):
 class Out(C.Structure):
     _fields_ = [("lines", C.c_char_p), ("len", C.c_size_t), ("cap", C.c_size_t), ("n_lines", C.c_uint64),
                 ("ip", P(C.c_uint32)), ("next_event_id", P(C.c_uint64)), ("next_packet_id", P(C.c_uint64)),
-                ("rng_probe", P(C.c_uint32)), ("mark_wall_s", C.c_double * 2)]
+                ("rng_probe", P(C.c_uint32)), ("mark_wall_s", C.c_double * 2),
+                ("obs", P(C.c_int64)), ("n_obs", C.c_uint64), ("cap_obs", C.c_uint64)]
+
+
+# ref_loop_out.obs: a row per TCP descriptor an echo process holds, each time
+# the process runs, after its connect call and before each of its closes --
+# tcp_getInfo's values
+OBS_FIELDS = ("t", "host", "proc", "local_ip", "local_port", "peer_ip", "peer_port",
+              "state", "cwnd", "ssthresh", "srtt", "rttvar")
+# tcpi_state is Linux's enum (netinet/tcp.h: TCP_ESTABLISHED = 1 ... TCP_CLOSING
+# = 11); _tcp_getTCPInfoState (tcp.c) maps tcp.c's enum TCPState onto it one to
+# one, so it maps back: the value is the index into shdgpu.TCP_STATE_NAMES
+LINUX_TO_TCPSTATE = {1: 4, 2: 2, 3: 3, 4: 5, 5: 6, 6: 8, 7: 0, 8: 9, 9: 10, 10: 1, 11: 7}
 
 
 _lib = None
+_observes = None
 
 
 def available() -> bool:
     return os.path.exists(LIB)
+
+
+def observes() -> bool:
+    """the built library records ref_loop_out.obs (one built before the
+    observation existed ignores the flag and gives no rows).  Read off the
+    file: the library itself is only ever loaded in run's child process."""
+    global _observes
+    if _observes is None:
+        _observes = available() and b"ref_loop_free_obs" in open(LIB, "rb").read()
+    return _observes
 
 
 def lib():
@@ -68,7 +91,7 @@ def _ptr(a, ct):
 
 
 def run(model: S.ModelArrays, g: S.GraphArrays, host_start=None, procs=None, tcp=None, quiet=False, echo=None,
-        marks=None, row_threads=0):
+        marks=None, row_threads=0, observe=False):
     """run_inproc in a forked child: the reference keeps process-wide state
     (the worker's thread-private object, glib quarks), so one run per process."""
     import multiprocessing as mp
@@ -77,7 +100,7 @@ def run(model: S.ModelArrays, g: S.GraphArrays, host_start=None, procs=None, tcp
 
     def child():
         try:
-            wr.send(("ok", run_inproc(model, g, host_start, procs, tcp, quiet, echo, marks, row_threads)))
+            wr.send(("ok", run_inproc(model, g, host_start, procs, tcp, quiet, echo, marks, row_threads, observe)))
         except BaseException as ex:   # noqa: BLE001 -- reported to the parent
             wr.send(("err", repr(ex)))
         wr.close()
@@ -96,9 +119,12 @@ def run(model: S.ModelArrays, g: S.GraphArrays, host_start=None, procs=None, tcp
 
 
 def run_inproc(model: S.ModelArrays, g: S.GraphArrays, host_start=None, procs=None, tcp=None, quiet=False,
-               echo=None, marks=None, row_threads=0):
+               echo=None, marks=None, row_threads=0, observe=False):
     """Run the model through the reference's loop; returns dict(lines=[(t, h, line)],
-    ip=[str], next_event_id, next_packet_id, rng_probe (uint arrays)).
+    ip=[str], next_event_id, next_packet_id, rng_probe (uint arrays); with
+    observe also obs=[[int] per OBS_FIELDS], the echo processes' TCP_INFO
+    observations, state in tcp.c's enum TCPState order (without it nothing is
+    observed and the loop pays nothing for it).
     host_start: [H] process start times (default: the model's app_start);
     procs: [(host, start)] processes in <process> order instead (the oracle's
     and the engine's pushed SHD_EV_APP_START events, in push order);
@@ -128,6 +154,7 @@ def run_inproc(model: S.ModelArrays, g: S.GraphArrays, host_start=None, procs=No
     cfg = Cfg()
     cfg.n_hosts = H
     cfg.quiet = 1 if quiet else 0
+    cfg.observe = 1 if observe else 0
     cfg.app = 0 if tcp is None else 1
     if getattr(model, "app_specs", None) is not None:   # app 3: the model's per-host datagram applications
         cfg.app = 3
@@ -208,11 +235,21 @@ def run_inproc(model: S.ModelArrays, g: S.GraphArrays, host_start=None, procs=No
                 h = by_ip[body.split(" -> ")[1].split(":")[0]]
             if h >= 0:   # (the scheduler's own boot messages have no host)
                 lines.append((int(t), h, body))
+        no = int(out.n_obs)
+        obs = np.ctypeslib.as_array(out.obs, shape=(no, len(OBS_FIELDS))).tolist() if no else []
+        i_st = OBS_FIELDS.index("state")
+        for row in obs:
+            row[i_st] = LINUX_TO_TCPSTATE[row[i_st]]
         res = dict(lines=lines, ip=ips,
                    next_event_id=np.ctypeslib.as_array(out.next_event_id, shape=(H,)).copy(),
                    next_packet_id=np.ctypeslib.as_array(out.next_packet_id, shape=(H,)).copy(),
                    rng_probe=np.ctypeslib.as_array(out.rng_probe, shape=(H,)).copy(), run_s=run_s,
                    mark_wall_s=(out.mark_wall_s[0], out.mark_wall_s[1]), rows_s=rows_s)
+        if observe:
+            res["obs"] = obs
+        if observe and observes():
+            lib().ref_loop_free_obs.argtypes = [P(Out)]
+            lib().ref_loop_free_obs(C.byref(out))
         lib().ref_loop_free(C.byref(out))
     finally:
         O.lib().o_topo_free(topo)

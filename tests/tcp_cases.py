@@ -154,8 +154,40 @@ CASES = {
 ECHO_CASES = [n for n in CASES if not n.startswith("mixed_")]
 
 
+def _hub3_slow():
+    """four hosts, a small tcp_hub_cases hub on very slow links: host 0 runs
+    three servers, hosts 1..3 a client each, 20000 bytes, 128 KiB/s both ways,
+    loss up to 0.05.  The hub's CoDel queue drops the clients' data and a
+    server's FIN reaches its client before the retransmitted data does: that
+    client's process runs again with its socket in CLOSEWAIT -- the one state
+    after ESTABLISHED that an echo process ever finds its socket in
+    (tests/golden/ref_tcp_snapshots.json)"""
+    n = 3
+    g = W.geometric_graph(12, seed=5, loss_max=0.05)
+    procs = [(0, SEC + i) for i in range(n)] + [(1 + i, 2 * SEC + i * 1000) for i in range(n)]
+    return dict(graph=g, hv=[0, 1, 2, 3], procs=procs, peers=[-1] * n + list(range(n)), nbytes=20000, end=40,
+                bw=dict(bw_down=128, bw_up=128))
+
+
+# cases of the snapshot fixture alone (tests/golden/ref_tcp_snapshots.json): kept
+# out of CASES, whose every entry has its lines in tests/golden/ref_tcp.json
+def _rto_reset():
+    """the heavy_loss pair at loss 0.3 with 20000 bytes: the client's first
+    data segment is lost three times over, its retransmission timer backs off
+    three times (reno's timeout each time: ssthresh halved, cwnd 10), and the
+    ACK that ends it resets srtt and rttvar to 0 (tcp.c's ACK processing,
+    backoff > 2) while the client still has data to send -- so its process
+    runs again and observes srtt 60 -> 0 at 6.3 s.  (An srtt of 1 ms, as on a
+    loopback pair, also reaches 0, by the estimator's integer arithmetic:
+    that is not this reset.)"""
+    return _pair(30.0, 0.3, 20000, 60)
+
+
+SNAPSHOT_CASES = {"hub3_slow": _hub3_slow, "rto_reset": _rto_reset}
+
+
 def build(name):
-    c = CASES[name]()
+    c = (CASES.get(name) or SNAPSHOT_CASES[name])()
     m = W.phold_model(np.asarray(c["hv"], dtype=np.int32), end_time=c["end"] * SEC, trace=True,
                       queue_flags=S.SHD_QF_TRACE_STATUS, load=0, payload=c.get("payload", 1), **c["bw"])
     return c, m

@@ -40,7 +40,11 @@ their first packet in the event that creates the socket, so that is the order
 of the first SND_CREATED lines of the host.
 
 The five snapshot fields (state, cwnd, ssthresh, srtt, rttvar) and proc are not
-in the lines; role is (0: the first packet is a SYN without ACK).
+in the lines; role is (0: the first packet is a SYN without ACK).  The five are
+pinned elsewhere: to the oracle's change log (tests/tcp_snapshot_expect.py,
+tests/test_tcp_snapshots_gpu.py), which holds the reference's tcp_getInfo values
+from a socket's creation until its process closes it
+(tests/test_tcp_snapshots_ref_cpu.py); after the close, oracle-to-device only.
 """
 import re
 

@@ -20,6 +20,12 @@ host, so each record is followed along its host's lines in their order: the
 sample of a touched record is taken when its next touch comes at or past the
 boundary, or at the end of the lines.
 
+The five snapshot fields of a sample (SNAPSHOT) are not in the lines: they are
+held to the oracle's change log just before the sample's boundary
+(tests/tcp_snapshot_expect.py, tests/test_tcp_snapshots_gpu.py), which is
+pinned to the reference's tcp_getInfo values from a socket's creation until
+its process closes it, and oracle-to-device only after the close.
+
 Rows are [flow, t, bytes_delivered, packets_created, bytes_created,
 retransmitted, inet_dropped, socket_dropped, router_dropped], flow the
 record's index in tcp_flow_expect.derive's order, sorted by (flow, t).

@@ -3,8 +3,11 @@ SHD_TCP_OPT_FLOWS, shd_tcp_result_flows; csrc/tcp.hip) against the reference's
 own loop: on every case of tests/golden/ref_tcp_flows.json the records of an
 untraced and of a traced run, with the path cache on the device and on tables,
 hold the fixture's pinned fields (tests/tcp_flow_expect.py derives them from
-the reference's [STATUS] lines); the five snapshot fields, which nothing the
-reference prints pins, are only required not to depend on the run's mode.
+the reference's [STATUS] lines); the five snapshot fields are required here not
+to depend on the run's mode, and their values are pinned by
+tests/test_tcp_snapshots_gpu.py (the oracle's change log, which holds the
+reference's tcp_getInfo values from a socket's creation until its process
+closes it; after the close, oracle-to-device only).
 Models without a fixture are compared with the records derived from the
 oracle's lines (oracle/o_tcp.c, pinned to the reference on the CPU)."""
 import ctypes as C
@@ -76,7 +79,7 @@ def test_flow_records_equal_the_reference(name, trace, mode):
 @pytest.mark.parametrize("name", list(FIX))
 def test_snapshot_fields_do_not_depend_on_the_mode(name):
     a = _run(name, *RUNS[0])["flows"]
-    assert (a["state"] <= 10).all() and (a["cwnd"] >= 1).all()
+    assert (a["state"] <= 10).all() and (a["cwnd"] >= 1).all()   # (the values: tests/test_tcp_snapshots_gpu.py)
     for trace, mode in RUNS[1:]:
         b = _run(name, trace, mode)["flows"]
         for k in FE.SNAPSHOT + ("proc",):

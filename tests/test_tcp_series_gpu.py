@@ -4,8 +4,10 @@ reference's own loop: on every case and interval of
 tests/golden/ref_tcp_series.json the samples of an untraced and of a traced
 run, with the path cache on the device and on tables, hold the fixture's rows
 (tests/tcp_series_expect.py derives them from the reference's [STATUS] lines);
-the five snapshot fields, which nothing the reference prints pins, are only
-required not to depend on the run's mode.  Models without a fixture are
+the five snapshot fields are required here not to depend on the run's mode;
+their values are pinned by tests/test_tcp_snapshots_gpu.py (the oracle's change
+log, which holds the reference's tcp_getInfo values from a socket's creation
+until its process closes it; after the close, oracle-to-device only).  Models without a fixture are
 compared with the rows derived from the oracle's lines (oracle/o_tcp.c, pinned
 to the reference on the CPU)."""
 import collections
@@ -73,7 +75,7 @@ def test_samples_equal_the_reference(name, us, trace, mode):
 @pytest.mark.parametrize("name,us", CASES)
 def test_snapshot_fields_do_not_depend_on_the_mode(name, us):
     a = _run(name, us, *RUNS[0])["series"]
-    assert (a["state"] <= 10).all() and (a["cwnd"] >= 1).all()
+    assert (a["state"] <= 10).all() and (a["cwnd"] >= 1).all()   # (the values: tests/test_tcp_snapshots_gpu.py)
     for trace, mode in RUNS[1:]:
         b = _run(name, us, trace, mode)["series"]
         for k in SE.SNAPSHOT:
