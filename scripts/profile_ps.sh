@@ -5,9 +5,7 @@
 #   the SQ counters per wave and round over the bench's timed region (two counter sets, no tracing),
 #   the kernel trace of the timed region against the bench's own time per round.
 #     scripts/profile_ps.sh <out dir> [<product library>] [<timing library>]
-# PS_TIMING_ARGS goes to scripts/ps_timing.py ("--convention events+1" for a timing library built with
-# -DSHD_NO_EXIT1, whose iteration count has the loop's empty last pass in it; "--exit" for one built
-# with -DSHD_TIMING_EXIT).
+# PS_TIMING_ARGS goes to scripts/ps_timing.py.
 set -o pipefail
 export TMPDIR=/tmp
 O=$1

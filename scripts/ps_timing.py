@@ -17,23 +17,13 @@ the round seen; k_round_ps also 21 the last flush's claims back and its stores
 issued, 22 the gather's poll passes, 23 the close's work under the last flush's
 path loads done (12 -> 23: the loads' issue and that work; 23 -> 13: what is
 left of their wait, and the resolve), 20 the round's end (what every block does
-between the gather's return and its next start).  With -DSHD_TIMING_EXIT added
-to a NOLOOP build (--exit here), slot 9 is the stamp of the fast round's due
-count and head known (1 -> 9: the scan of the staged list, or what is left of
-it) and slot 8 the time of the loop's last pass when no lane ran an event or
-worked in it (the pass the loop no longer makes: only a build with
--DSHD_NO_EXIT1 has such passes).  With -DSHD_TIMING_CARRY added to a NOLOOP
-build instead (--carry here), slot 9 is 1 + (the block's last flush had a near
-delivery under the far rule of ps_loop_close's CARRY: one whose stores the
-share waits for) + 2 x (it had a far one); a library built with -DSHD_NO_CARRY
-applies the same rule without acting on it.
+between the gather's return and its next start).
 
-The iteration count (slot 16) follows the library: a loop that leaves with
-its last event (the default) counts the busiest lane's events, the loop built
-with -DSHD_NO_EXIT1 and every file under profiles/iter/ one more, the pass that
-finds nothing left; --convention names which one the library at hand has, and
-the report repeats it beside the counts and the fit.  Printed relative to the round's earliest start: mean over
-rounds of the mean and the max over blocks; and the phase durations.
+The iteration count (slot 16) is the busiest lane's events: the loop leaves
+with its last event (the files under profiles/iter/ are older and count one
+more, the pass that found nothing left).  Printed relative to the round's
+earliest start: mean over rounds of the mean and the max over blocks; and the
+phase durations.
 """
 import ctypes as C
 import os
@@ -54,11 +44,6 @@ def main():
     ap.add_argument("--at", type=float, default=2.0, help="simulated seconds before the measured rounds")
     ap.add_argument("--workload", choices=["c3", "c5"], default="c3",
                     help="c5: bench.py's C5 model at --hosts hosts (the per-GPU shard: 125000; k_round_sp)")
-    ap.add_argument("--convention", choices=["events", "events+1"], default="events",
-                    help="what the library's iteration count is: the busiest lane's events (the default build) or one "
-                         "more (-DSHD_NO_EXIT1, and the files under profiles/iter/)")
-    ap.add_argument("--exit", action="store_true", help="the library is a -DSHD_TIMING_EXIT build (slots 8 and 9)")
-    ap.add_argument("--carry", action="store_true", help="the library is a -DSHD_TIMING_CARRY build (slot 9)")
     a = ap.parse_args()
     import torch
     torch.cuda.set_device(0)
@@ -161,22 +146,6 @@ def main():
               f"{np.mean([a.max() for a, _, _ in cr]):.2f} us; loop done -> there {np.mean([b.mean() for _, b, _ in cr]):.2f} us, "
               f"there -> close done {np.mean([c.mean() for _, _, c in cr]):.2f} us; publish drain (close done -> published) "
               f"mean {np.mean([d.mean() for d in dr]):.2f} / max {np.mean([d.max() for d in dr]):.2f} us")
-    # the last flush's deliveries under the far rule (--carry; slot 9: 1 + near + 2 x far), per
-    # block-round that flushed, and in the round's slowest block (the last to publish)
-    kinds, slow = [], []
-    for r in range(64 if a.carry else 0):
-        x = t_all[r]
-        t0 = x[:, 0].min()
-        ok = (t0 > 0) & (x[:, 21] >= x[:, 4]) & (x[:, 4] >= t0) & (x[:, 6] >= x[:, 21]) & (x[:, 9] >= 1) & (x[:, 9] <= 4)
-        if ok.any():
-            kinds += list(x[ok, 9] - 1)
-            slow.append(int(x[ok, 9][np.argmax(x[ok, 6])]) - 1)
-    if kinds:
-        kinds, slow = np.array(kinds), np.array(slow)
-        print(f"  last flush under the far rule: {len(kinds)} block-rounds, with a near delivery "
-              f"{np.mean((kinds & 1) != 0) * 100:.1f} %, with a far one {np.mean((kinds & 2) != 0) * 100:.1f} %, with "
-              f"none {np.mean(kinds == 0) * 100:.1f} %; the round's slowest block (the last to publish) had a near one "
-              f"in {int(((slow & 1) != 0).sum())} of {len(slow)} rounds ({np.mean((slow & 1) != 0) * 100:.1f} %)")
     # the close under the last flush's path loads (12 -> 23 -> 13), in blocks that flushed
     gp = []
     for r in range(64):
@@ -220,7 +189,7 @@ def main():
         dur += list((x[ok, 4] - x[ok, 2]) / 100.0)
     if it:
         it, nfl, nact, dur, seg = map(np.array, (it, nfl, nact, dur, seg))
-        print(f"  loop (iterations = the busiest lane's {a.convention}): iterations mean {it.mean():.2f} max {it.max()}; flushes mean {nfl.mean():.2f}; "
+        print(f"  loop (iterations = the busiest lane's events): iterations mean {it.mean():.2f} max {it.max()}; flushes mean {nfl.mean():.2f}; "
               f"active lanes mean {nact.mean():.1f}; loop us mean {dur.mean():.2f}")
         for k in sorted(set(it.tolist()))[:12]:
             sel = it == k
@@ -236,29 +205,12 @@ def main():
         one = (nfl == 1) & (it >= 1)
         if len(set(it[one].tolist())) > 1:
             s4, i4 = np.polyfit(it[one], dur[one], 1)
-            line = f"    per iteration (iterations = {a.convention}; slope over {int(one.sum())} block-rounds): loop done - bins merged {s4:.3f} us (+ {i4:.2f})"
+            line = f"    per iteration (iterations = events; slope over {int(one.sum())} block-rounds): loop done - bins merged {s4:.3f} us (+ {i4:.2f})"
             ok3 = one & ~np.isnan(lend)
             if len(set(it[ok3].tolist())) > 1:
                 s3, i3 = np.polyfit(it[ok3], lend[ok3], 1)
                 line += f"; last flush starts - bins merged {s3:.3f} us (+ {i3:.2f})"
             print(line)
-    # the loop's two ends (--exit): the fast round's scan of the staged list (1 -> 9), and the last pass
-    # when it is empty (slot 8: cycles + 1; 1: the last pass ran an event)
-    scan, emp, nlast = [], [], 0
-    for r in range(64 if a.exit else 0):
-        x = t_all[r]
-        t0 = x[:, 0].min()
-        ok = (t0 > 0) & (x[:, 1] >= t0) & (x[:, 9] >= x[:, 1]) & (x[:, 2] >= x[:, 9])
-        scan += list((x[ok, 9] - x[ok, 1]) / 100.0)
-        ok = (t0 > 0) & (x[:, 4] >= x[:, 2]) & (x[:, 2] >= t0) & (x[:, 8] >= 1) & (x[:, 8] < 100000)
-        nlast += int(ok.sum())
-        emp += list((x[ok & (x[:, 8] > 1), 8] - 1) / 100.0)
-    if scan:
-        print(f"  fast rounds: words read -> due count and head known mean {np.mean(scan):.3f} us, max {np.max(scan):.2f} "
-              f"({len(scan)} block-rounds)")
-    if nlast:
-        print(f"  the loop's last pass with no event and no work (a -DSHD_TIMING_EXIT build): {len(emp)} of {nlast} "
-              f"block-rounds" + (f", mean {np.mean(emp):.3f} us, max {np.max(emp):.2f}" if emp else ""))
     # k_round_sp: active hosts (20) and passes (21) per block and round
     na, npas = [], []
     for r in range(64):

@@ -446,6 +446,13 @@ __shared__ uint32_t s_tslot;
 #define TIMVP(k, v)
 #define TCNT(i)
 #endif
+// the persistent rounds' stamps of the SHD_TIMING_LIGHT build alone (slots the
+// full timing build uses otherwise)
+#ifdef SHD_TIMING_LIGHT
+#define TIMPL(k) TIMP(k)
+#else
+#define TIMPL(k)
+#endif
 #ifdef SHD_PROF
 __device__ unsigned long long g_prof[2 * PR_N + 2];
 // per-round wave timing (100 MHz wall clock), 128 round slots keyed by the
@@ -496,8 +503,16 @@ __device__ __forceinline__ T launder(T x) {
 }
 // the same for a wave-uniform value, kept in an SGPR: branches on it are
 // scalar branches, so a feature that is off costs a compare and a jump, and
-// the loads behind it are skipped rather than issued under an empty exec mask
+// the loads behind it are skipped rather than issued under an empty exec mask.
+// (The timing builds' readfirstlane: k_round, whose Params come by value,
+// reads them from a scratch copy there -- a vector load -- and the asm's
+// operand then has no other way into an SGPR: the backend stops with "illegal
+// VGPR to SGPR copy".  Not in the product: the general kernels' register
+// allocation moves with it.)
 __device__ __forceinline__ uint32_t launder_s(uint32_t x) {
+#ifdef SHD_TIMING
+    x = (uint32_t)__builtin_amdgcn_readfirstlane((int)x);
+#endif
     asm volatile("" : "+s"(x));
     return x;
 }
@@ -1353,9 +1368,7 @@ __device__ __forceinline__ void flush_wave(const DParams& P, HostCtx& c, bool de
     s_att[lane] = c.att;
     s_cls[lane] = c.cls;
     __syncthreads();
-#ifdef SHD_TIMING_LIGHT
-    TIMP(12);
-#endif
+    TIMPL(12);
     uint32_t err = 0;
     for (uint32_t base = 0; base < total; base += kBlock) {
         const uint32_t r = base + lane;
@@ -1415,9 +1428,7 @@ __device__ __forceinline__ void flush_wave(const DParams& P, HostCtx& c, bool de
         }
     }
     __syncthreads();
-#ifdef SHD_TIMING_LIGHT
-    TIMP(13);
-#endif
+    TIMPL(13);
     // per host, in send order (worker.c:286-320).  Timers scheduled since the
     // last flush hold provisional IDs: an ID x loses the dropped sends issued
     // before it
@@ -1467,9 +1478,7 @@ __device__ __forceinline__ void flush_wave(const DParams& P, HostCtx& c, bool de
     c.ns = 0;
     __syncthreads();
     if (lane == 0) s_pool_n = 0;   // (every lane read it above, before the barrier)
-#ifdef SHD_TIMING_LIGHT
-    TIMP(14);
-#endif
+    TIMPL(14);
     // deliveries: calendar claims for 64 events at a time, then the stores.
     // The round's last flush (one batch) only issues the claims, in the
     // resolve loop: the per-host walk hides their round trip, and the stores
@@ -1684,9 +1693,7 @@ __device__ __forceinline__ void flush_last_issue(const DParams& P, HostCtx& c, u
     s_att[lane] = c.att;
     s_cls[lane] = c.cls;
     __syncthreads();
-#ifdef SHD_TIMING_LIGHT
-    TIMP(12);
-#endif
+    TIMPL(12);
     s.valid = lane < total;
     s.q = SendRec{};
     s.a = 0; s.b = 0; s.dst = 0; s.ra = 0;
@@ -1714,15 +1721,11 @@ __device__ __forceinline__ void flush_last_consume(const DParams& P, HostCtx& c,
         if (del) flush_claim(P, c, e, pd);
     }
     __syncthreads();
-#ifdef SHD_TIMING_LIGHT
-    TIMP(13);
-#endif
+    TIMPL(13);
     flush_walk<PS>(P, c, c.ns);
     __syncthreads();
     if (threadIdx.x == 0) s_pool_n = 0;
-#ifdef SHD_TIMING_LIGHT
-    TIMP(14);
-#endif
+    TIMPL(14);
     c.err |= err;
 }
 
@@ -1955,7 +1958,6 @@ __device__ void begin_event(const DParams& P, HostCtx& c, const shd_event& e) {
     c.q_sub = 0;
     c.w_msgs = 0;
     c.w_fl = 0;
-#ifndef SHD_NO_EVFAST
     // The steady-state arrival, straight-line: a packet that meets an empty
     // router queue with room in the receive bucket at a listening host (no
     // tracing, past the bootstrap period) is enqueued, dequeued at once
@@ -1995,7 +1997,6 @@ __device__ void begin_event(const DParams& P, HostCtx& c, const shd_event& e) {
         refill_fast(P, c);
         return;
     }
-#endif
     switch (e.kind) {
     case SHD_EV_HEARTBEAT:
         // tracker_heartbeat (tracker.c:566-611): the node counters at the k-th
@@ -2310,18 +2311,17 @@ __device__ __forceinline__ void arrival_fast(const DParams& P, HostCtx& c, uint3
 // host's next and in the window), then the refill under the same rule: what
 // take_next, begin_event and the loop's fused notification and refill do for
 // it, with the same functions in the same order (but the send's place in the
-// pool: worker_send_placed).  True for the lanes that took it (a lane with
-// nothing left before `we` among them: it is done); the others (a tie, a heap
-// event, a backlog, a full pool, a lane at work) are left untouched for the
-// general iteration.  The choice is per lane: per wave, by one ballot, so that
-// one lane that cannot sends the wave's iteration the general way, measured
-// no better.
+// pool: worker_send_placed).  True for the lanes that took it; the others (a
+// tie, a heap event, a backlog, a full pool, a lane at work) are left
+// untouched for the general iteration.  The choice is per lane: per wave, by
+// one ballot, so that one lane that cannot sends the wave's iteration the
+// general way, measured no better.
 //
-// CARRIED (the loop that leaves in the iteration of its last event,
-// ps_loop_close): `ct` is the lane's candidate time, next_cand() of the state
-// the previous iteration left, for the lanes in state 0 -- all of them before
-// `we`, the others were retired where it was worked out -- so the minimum is
-// not taken again here and no lane ends here.
+// `ct` (the loop leaves in the iteration of its last event, ps_loop): the
+// lane's candidate time, next_cand() of the state the previous iteration left,
+// for the lanes in state 0 -- all of them before `we`, the others were retired
+// where it was worked out -- so the minimum is not taken again here and no
+// lane ends here.
 // (next_cand: the earliest of the lane's five candidate times, take_next's t)
 __device__ __forceinline__ uint64_t next_cand(const HostCtx& c) {
     const uint64_t ht = c.evq_n ? c.top_time : kInf;
@@ -2330,10 +2330,9 @@ __device__ __forceinline__ uint64_t next_cand(const HostCtx& c) {
     const uint64_t qt = c.dt < ht ? c.dt : ht;
     return bt < qt ? bt : qt;
 }
-template <bool CARRIED = false>
-__device__ __forceinline__ bool steady_iter(const DParams& P, HostCtx& c, uint64_t we, uint32_t& st, uint64_t ct = 0) {
+__device__ __forceinline__ bool steady_iter(const DParams& P, HostCtx& c, uint64_t we, uint32_t& st, uint64_t ct) {
     const uint64_t ht = c.evq_n ? c.top_time : kInf;
-    const uint64_t t = CARRIED ? ct : next_cand(c);
+    const uint64_t t = ct;
     const uint32_t neq = (uint32_t)(c.tt0 == t) + (uint32_t)(c.tt1 == t) + (uint32_t)(c.tt2 == t) +
                          (uint32_t)(c.dt == t) + (uint32_t)(ht == t);
     const bool u = st == 0u && t < we && neq == 1u;
@@ -2351,11 +2350,9 @@ __device__ __forceinline__ bool steady_iter(const DParams& P, HostCtx& c, uint64
     const bool sa = u && c.dt == t && d.kind == SHD_EV_PACKET && arrival_fast_ok(P, c);
     const bool sn = u && c.tt2 == t && notify_fast_ok_room(P, c, room);
     const bool sr = u && c.tt1 == t && c.cq_count == 0 && c.tq_count == 0;
-    const bool end = !CARRIED && st == 0u && t >= we;   // nothing left before the window's end: the lane is done
     c.now = now0;
-    const bool sdy = sa || sn || sr || end;
+    const bool sdy = sa || sn || sr;
     if (!sdy) return false;
-    if (end) st = 3u;
     if (sa) {
         c.dh++;
         c.dt = c.dh < c.nd ? dt1 : kInf;

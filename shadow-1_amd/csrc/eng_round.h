@@ -431,7 +431,6 @@ __device__ __forceinline__ void round_body(const DParams& P, const HostIn& in, u
                         i_be = clock64();
 #endif
                         st = ((c.w_fl & ~W_READ) | c.w_msgs) ? 1u : 0u;   // the shared steps, if any are left
-#ifndef SHD_NO_FUSE
                         // An arrival schedules its notification at +1 ns, and
                         // that is almost always the host's next event: when the
                         // notification timer is strictly the earliest candidate
@@ -466,7 +465,6 @@ __device__ __forceinline__ void round_body(const DParams& P, const HostIn& in, u
                                 refill_fast(P, c);
                             }
                         }
-#endif
                     } else {
                         st = 3u;
                     }
@@ -1141,7 +1139,7 @@ __device__ __forceinline__ void ps_prologue(const DParams& P, HostCtx& c, bool a
 // `we` are this round's -- and the span of the previous round's close bitmap
 // (pspan) names the window's non-empty bins.  The bins wholly consumed are reset as
 // in ps_prologue; their bits go to clr (bit j: bin b0 + j), cleared from the
-// bitmap loaded at this round's start once it has landed (ps_loop_close).
+// bitmap loaded at this round's start once it has landed (ps_close_pf).
 //
 // AHEAD: the count starts at what the staging counted (du, pf_stage): the
 // first du.n0 events are before the previous window's end + the window, which
@@ -1174,9 +1172,6 @@ __device__ __forceinline__ void ps_prologue_pf(const DParams& P, HostCtx& c, boo
             c.dt = nd ? s_due[threadIdx.x].time : kInf;
         }
     }
-#ifdef SHD_TIMING_EXIT
-    TIMP(9);   // the fast round's due count and head known (slot 9 is free in a NOLOOP build)
-#endif
     if (active) {
 #pragma unroll
         for (uint32_t j = 0; j < 3; j++) {
@@ -1203,7 +1198,7 @@ struct PfBins {
 // load, whatever its bitmap says: a lane without the bin reads past the
 // resource's end, which the buffer's range check answers with zeros and no
 // memory access.  So the compiler knows how many loads these are, and a wait
-// for loads issued ahead of them (the last flush's path loads, ps_loop_close)
+// for loads issued ahead of them (the last flush's path loads, ps_close_pf)
 // does not take these in -- behind loads under a branch it would wait for all
 constexpr uint32_t kPfPast = 0x40000000u;   // past any block's bins (64 hosts: 2 MB)
 __device__ __forceinline__ void pf_issue(const PsRsrc& R, uint32_t lb, uint64_t b, uint64_t sp, bool has, PfBins& pb) {
@@ -1281,353 +1276,330 @@ __device__ __forceinline__ uint32_t ps_window_bits(const DParams& P, HostCtx& c,
     const uint64_t sp = P.bins ? bm_span(w, (uint32_t)(ws >> P.bin_shift) & (kNB - 1)) : 0ull;
     return ps_window_bits(P, c, sp, 0u, ws, we);
 }
-// cal_lower_bound with the bitmap's span from we's bin on at hand (HAVE; bm_span):
+// cal_lower_bound with the bitmap's span from we's bin on at hand (bm_span):
 // the span's first set bit is the bitmap's first from there on when it has
 // one (a host with a calendar event within 33 bins: nearly every one), and the
 // eight-word scan is left to the lanes whose span is empty
-template <bool HAVE>
 __device__ __forceinline__ uint64_t cal_lower_bound_sp(const DParams& P, const uint32_t (&w)[kNBW], uint64_t sp,
                                                        uint64_t we) {
-    if (!HAVE || sp == 0) return cal_lower_bound(P, w, we);
+    if (sp == 0) return cal_lower_bound(P, w, we);
     const uint64_t t = ((we >> P.bin_shift) + (uint32_t)__builtin_ctzll(sp)) << P.bin_shift;
     return t > we ? t : we;
 }
 
-// The round's event loop (as round_body's: per-lane state 0 needs its next
-// event, 1 runs one, 2 waits for a flush, 3 done; wave-uniform exits only)
-// and its close: the lane's next time (an idle lane's from its timers and
-// bitmap), worked out under the last flush's path loads, then the last
-// flush's stores.  PF: clr (bit j: ring position clr_p + j)
-// is cleared from w first (bins the prologue reset, when w was loaded in
-// parallel), and the next window's bins are loaded in the close, into *pb;
-// *span: the bitmap's span from we's bin on, for the next round.  fin: the
-// caller's own work on what is final once the loop has ended (the whole wave
-// calls it, in the close)
-struct PsNoFin {
-    __device__ __forceinline__ void operator()() const {}
-};
-// STEADY (the lean k_round_ps): the steady iteration (steady_iter, eng_device.h)
-// ahead of the general one, which the lanes it does not take run unchanged.
+// The persistent round's clock reads inside its event loop (the timing
+// build): empty functions in every other build, as ProfAcc / PROF_ADD.
 // SHD_TIMING_NOLOOP: the timing build without the clock reads inside the loop
 // (the stamps and the iteration count stay), for the product's cost per iteration.
 #if defined(SHD_TIMING_LIGHT) && !defined(SHD_TIMING_NOLOOP)
 #define SHD_TIMING_INLOOP 1
 #endif
-// EXIT (the lean k_round_ps): the loop leaves in the iteration that
-// ran the wave's last event.  The lane's candidate time (next_cand) is worked
-// out before the loop and again at the bottom of every iteration, for the
-// lanes in state 0, from the state the iteration left -- behind the general
-// iteration and run_work, so nothing lies between its computation and its use
-// at the next iteration's top (a flush inside the loop runs when every lane is
-// in state 2 or 3, and the lanes it sets to 1 get a new candidate behind their
-// run_work) -- and a lane whose candidate is not before `we` (take_next's
-// test) is done there: the exit ballot fires in that iteration, without a
-// pass in which no lane runs an event, and a wave without an active lane
-// does not enter the loop.  steady_iter takes the carried candidate in place
-// of its own minimum.
+struct LoopTim {
+#ifdef SHD_TIMING_LIGHT
+    uint32_t n_it = 0, n_fl = 0;
+    unsigned long long t_take = 0, t_work = 0, t_fl = 0, ta = 0, tq = 0, t_q[3] = {0, 0, 0};
+#endif
+#ifdef SHD_TIMING_INLOOP
+    __device__ __forceinline__ void lap(unsigned long long& acc, unsigned long long& t0) {
+        const unsigned long long t = wall_clock64();
+        acc += t - t0;
+        t0 = t;
+    }
+    __device__ __forceinline__ void iter() { n_it++; ta = wall_clock64(); }
+    __device__ __forceinline__ void take() { tq = wall_clock64(); }
+    __device__ __forceinline__ void took() { lap(t_q[0], tq); }     // take_next
+    __device__ __forceinline__ void began() { lap(t_q[1], tq); }    // begin_event
+    __device__ __forceinline__ void fuse() { tq = wall_clock64(); }
+    __device__ __forceinline__ void fused() { lap(t_q[2], tq); }    // the fused notification
+    __device__ __forceinline__ void events() { lap(t_take, ta); }   // take_next + begin_event + the fused events
+    __device__ __forceinline__ void worked() { lap(t_work, ta); }   // run_work
+    __device__ __forceinline__ void flush() { n_fl++; ta = wall_clock64(); }
+    __device__ __forceinline__ void flushed(bool last) { if (!last) lap(t_fl, ta); }   // the flushes before the last
+#else
+#ifdef SHD_TIMING_LIGHT
+    __device__ __forceinline__ void iter() { n_it++; }
+    __device__ __forceinline__ void flush() { n_fl++; }
+#else
+    __device__ __forceinline__ void iter() {}
+    __device__ __forceinline__ void flush() {}
+#endif
+    __device__ __forceinline__ void take() {}
+    __device__ __forceinline__ void took() {}
+    __device__ __forceinline__ void began() {}
+    __device__ __forceinline__ void fuse() {}
+    __device__ __forceinline__ void fused() {}
+    __device__ __forceinline__ void events() {}
+    __device__ __forceinline__ void worked() {}
+    __device__ __forceinline__ void flushed(bool) {}
+#endif
+    // the loop's end: stamp 4 and the loop's figures (slots as scripts/ps_timing.py reads them)
+    __device__ __forceinline__ void done(const DParams& P, bool active) {
+        TIMP(4);
+#ifdef SHD_TIMING_LIGHT
+        TIMVP(16, (uint64_t)n_it);   // loop iterations of the wave
+        TIMVP(17, (uint64_t)n_fl);   // flushes
+        TIMVP(18, (uint64_t)__popcll(__ballot(active)));
+        TIMVP(8, t_take);    // in take_next + begin_event (+ the fused notification / refill)
+        TIMVP(9, t_work);    // in run_work
+        TIMVP(10, t_fl);     // in the flushes before the last
+        TIMVP(11, t_q[0]);   // of 8: take_next
+        TIMVP(15, t_q[1]);   //       begin_event
+        TIMVP(19, t_q[2]);   //       the fused notification (the rest: the fused refill, the loop's own)
+#endif
+    }
+};
+// what the loop leaves to the round's close
+struct PsLoopEnd {
+    PendDel pd;       // the delivery a flush claimed and has not stored yet (flush_wave, flush_last_consume)
+    LoopTim tm;
+};
+
+// The persistent round's event loop (as round_body's: per-lane state 0 needs
+// its next event, 1 runs one, 2 waits for a flush, 3 done; wave-uniform exits
+// only), with the flushes before the last.  The last flush runs here too,
+// whole, its delivery's stores left to the close (le.pd) -- but for LASTOUT
+// (k_round_ps): there a last flush of one batch is left to the close
+// altogether (the loop returns its sends, else 0; ps_close_pf takes it in two
+// steps around its own work), and one of more than one batch runs here, whole
+// and not deferred: its deliveries go out with it, and le.pd stays empty.
 //
-// CARRY (k_round_ps; PF): the last flush's far deliveries complete behind the
-// share.  The block's next time N -- the wave's least `next` and min_emit, and
-// the bound carried from the previous round's far deliveries (cy->carry): the
-// value its share publishes -- is folded before the stores (under the claims'
-// round trip) and comes back in `next`, wave-uniform.  Every block's N is at
-// least the gather's fold, so the next window ends at or before lim = min(N +
-// window, stop), and before the barrier after next a receiver reads no bin
-// from b(lim) + kPfBins on: not this round's prefetch (pf_lim is not behind
-// it), not the next window, not the next round's prefetch.  The deliveries
-// into those bins are issued last (flush_finish_far) and ps_publish leaves
-// them in flight; the next round's share drains them, being younger.  The
-// bitmap a receiver loads at the next round's start may so miss a far
-// delivery's bit, which stands for the bin's start in that round's next time:
-// the sender publishes it in its place (cy->far_t, folded by the caller into
-// the next round's cy->carry).
+// STEADY (the lean k_round_ps): the steady iteration (steady_iter,
+// eng_device.h) ahead of the general one, which the lanes it does not take run
+// unchanged; and the loop leaves in the iteration that ran the wave's last
+// event.  The lane's candidate time (next_cand) is worked out before the loop
+// and again at the bottom of every iteration, for the lanes in state 0, from
+// the state the iteration left -- behind the general iteration and run_work,
+// so nothing lies between its computation and its use at the next iteration's
+// top (a flush inside the loop runs when every lane is in state 2 or 3, and
+// the lanes it sets to 1 get a new candidate behind their run_work) -- and a
+// lane whose candidate is not before `we` (take_next's test) is done there:
+// the exit ballot fires in that iteration, without a pass in which no lane
+// runs an event, and a wave without an active lane does not enter the loop.
+// steady_iter takes the carried candidate in place of its own minimum.
+//
+// HR (eng_device.h): false in the LEAN kernels.
+template <bool LASTOUT, bool STEADY, bool XCH, bool HR>
+__device__ __forceinline__ uint32_t ps_loop(const DParams& P, HostCtx& c, bool active, uint64_t we, PsLoopEnd& le) {
+    static_assert(!STEADY || (LASTOUT && !HR), "the steady iteration is the lean k_round_ps's");
+    static_assert(!LASTOUT || (!XCH && STEADY != HR), "k_round_ps: no exchange; lean with STEADY, general with HR");
+    LoopTim& tm = le.tm;
+    le.pd.kind = 0;
+    uint32_t total = 0;   // LASTOUT: the sends of a one-batch last flush, left to the close (0: none left)
+    uint32_t st = active ? 0u : 3u;
+    uint64_t ct = 0;   // STEADY: the candidate time of a lane in state 0
+    if (STEADY) {
+        ct = next_cand(c);
+        if (st == 0u && ct >= we) st = 3u;
+    }
+    for (;;) {
+        if (!STEADY || __ballot(st <= 1u) != 0)
+        for (;;) {
+            tm.iter();
+            bool sdy = false;
+            if (STEADY) sdy = steady_iter(P, c, we, st, ct);
+            if (st == 0u && !sdy) {
+                shd_event e;
+                tm.take();
+                const bool got = take_next(P, c, we, e);
+                tm.took();
+                if (got) {
+                    c.now = e.time;
+                    begin_event<HR>(P, c, e);
+                    tm.began();
+                    st = ((c.w_fl & ~W_READ) | c.w_msgs) ? 1u : 0u;
+                    tm.fuse();
+                    if (st == 0u && c.tt2 < we) {   // the notification, when it is next (round_body)
+                        const uint64_t t = c.tt2, ht = c.evq_n ? c.top_time : kInf;
+                        if (t < c.tt0 && t < c.tt1 && t < c.dt && t < ht && notify_fast_ok<HR>(P, c)) {
+                            c.tt2 = kInf; c.now = t; c.c_events++;
+                            c.q_seq = c.ts2; c.q_src = c.h; c.q_sub = 0;
+                            c.w_msgs = 0; c.w_fl = 0;
+                            notify_fast(P, c);
+                            st = c.w_fl ? 1u : 0u;
+                        }
+                    }
+                    tm.fused();
+                    if (st == 0u && c.tt1 < we) {   // the periodic refill, when it is next
+                        const uint64_t t = c.tt1, ht = c.evq_n ? c.top_time : kInf;
+                        if (t < c.tt0 && t < c.tt2 && t < c.dt && t < ht && c.cq_count == 0 && c.tq_count == 0) {
+                            c.tt1 = kInf; c.now = t; c.c_events++;
+                            c.q_seq = c.ts1; c.q_src = c.h; c.q_sub = 0;
+                            c.w_msgs = 0; c.w_fl = 0;
+                            refill_fast(P, c);
+                        }
+                    }
+                } else {
+                    st = 3u;
+                }
+            }
+            tm.events();
+            if (st == 1u) st = run_work<HR>(P, c) ? 0u : 2u;
+            tm.worked();
+            if (STEADY && st == 0u) {
+                ct = next_cand(c);
+                if (ct >= we) st = 3u;
+            }
+            if (__ballot(st <= 1u) == 0) break;
+        }
+        const bool last = __ballot(st == 2u) == 0;
+        if (last) { TIMP(3); }   // (the timing builds' stamp: the round's last flush starts)
+        tm.flush();
+        if (LASTOUT && last) {
+            total = flush_total();
+            if (total <= (uint32_t)kBlock) break;
+            total = 0;
+        }
+        flush_wave<true, XCH>(P, c, !LASTOUT && last, le.pd);
+        tm.flushed(last);
+        if (last) break;
+        if (st == 2u) st = 1u;
+    }
+    return total;
+}
+
+// The sparse passes' close (k_round_sp / k_round_spx: a few sends each and
+// next to no close to put under them; the two-step last flush measured 2 %
+// slower there): the last flush's stores, then the lane's next time.
+template <bool XCH>
+__device__ __forceinline__ void ps_close(const DParams& P, HostCtx& c, bool active, uint64_t we,
+                                         const uint32_t (&w)[kNBW], uint64_t& next, PsLoopEnd& le) {
+    le.tm.done(P, active);
+    flush_finish<XCH>(P, c, le.pd);
+    if (active) {   // (the consumed bins were cleared in w)
+        next = host_next(c);
+        if (P.bins) {
+            const uint64_t cb = cal_lower_bound(P, w, we);
+            next = cb < next ? cb : next;
+        }
+    }
+    if (active && c.min_emit < next) next = c.min_emit;
+    TIMP(5);
+}
+
+// k_round_ps's close: the lane's next time (an idle lane's from its timers and
+// bitmap) and the next window's prefetch, worked out under the last flush's
+// path loads, then the last flush's stores.  clr (bit j: ring position clr_p +
+// j) is cleared from w first (bins the prologue reset, when w was loaded in
+// parallel); the next window's bins (from b1, we's bin, on) are loaded into
+// pb; span: the bitmap's span from we's bin on, for the next round.  fin: the
+// caller's own work on what is final once the loop has ended (the whole wave
+// calls it).
+//
+// The last flush's path loads go out first and the close runs while they are
+// in flight: it needs nothing of the flush but min_emit, and the flush nothing
+// of it (pf_lim is the round's).  The next window's bins may so be loaded
+// ahead of this wave's own deliveries into them: those are noted as every
+// other block's (note_dirty in flush_finish, before ps_noted reads the list),
+// and a noted host reads its window again.  The prefetch loads follow the path
+// loads (ahead of them they delay the resolve by their own round trip: loads
+// return in order), and are countable (pf_issue), so the resolve waits for the
+// path loads alone.
+//
+// The last flush's far deliveries complete behind the share.  The block's next
+// time N -- the wave's least `next` and min_emit, and the bound carried from
+// the previous round's far deliveries (cy.carry): the value its share
+// publishes -- is folded before the stores (under the claims' round trip) and
+// comes back in `next`, wave-uniform.  Every block's N is at least the
+// gather's fold, so the next window ends at or before lim = min(N + window,
+// stop), and before the barrier after next a receiver reads no bin from b(lim)
+// + kPfBins on: not this round's prefetch (pf_lim is not behind it), not the
+// next window, not the next round's prefetch.  The deliveries into those bins
+// are issued last (flush_finish_far) and ps_publish leaves them in flight; the
+// next round's share drains them, being younger.  The bitmap a receiver loads
+// at the next round's start may so miss a far delivery's bit, which stands for
+// the bin's start in that round's next time: the sender publishes it in its
+// place (cy.far_t, folded by the caller into the next round's cy.carry).
 struct PsCarry {
     uint64_t window, stop;
     uint64_t carry;   // in: the earliest bin start of the previous round's far deliveries (kInf: none)
     uint64_t far_t;   // out: the lane's far delivery time (kInf: none)
     bool any;         // out: the wave issued a far group
 };
-// HR (eng_device.h): false in the LEAN kernels.
-template <bool PF, bool XCH = true, class Fin = PsNoFin, bool STEADY = false, bool EXIT = false, bool CARRY = false,
-          bool HR = true>
-__device__ __forceinline__ void ps_loop_close(const DParams& P, HostCtx& c, bool active, bool has, const PsRsrc& R,
-                                              uint32_t lb, uint64_t we, uint32_t (&w)[kNBW], uint32_t clr_p,
-                                              uint32_t clr, uint64_t& next, PfBins* pb, uint64_t* span,
-                                              const Fin& fin = Fin{}, PsCarry* cy = nullptr) {
-    static_assert(PF || !CARRY, "the far group is the two-step last flush's");
-    PendDel pd;
-    pd.kind = 0;
-    uint32_t total = 0;   // the sends of a last flush of one batch
-#ifdef SHD_TIMING_LIGHT
-    uint32_t n_it = 0, n_fl = 0;
-    unsigned long long t_take = 0, t_work = 0, t_fl = 0, ta = 0, t_q[3] = {0, 0, 0};
-#endif
-#ifdef SHD_TIMING_EXIT   // (with SHD_TIMING_NOLOOP: slots 8 and 9 are free there)
-    unsigned long long tx = 0, t_empty = 0;
-    uint32_t ev0 = 0;
-    bool work = false;
-#endif
-    {
-        uint32_t st = active ? 0u : 3u;
-        uint64_t ct = 0;   // EXIT: the candidate time of a lane in state 0
-        if (EXIT) {
-            ct = next_cand(c);
-            if (st == 0u && ct >= we) st = 3u;
-        }
-        for (;;) {
-            if (!EXIT || __ballot(st <= 1u) != 0)
-            for (;;) {
-#ifdef SHD_TIMING_LIGHT
-                n_it++;
-#endif
-#ifdef SHD_TIMING_INLOOP
-                ta = wall_clock64();
-#endif
-#ifdef SHD_TIMING_EXIT
-                tx = wall_clock64();
-                ev0 = c.c_events;
-                work = __ballot(st == 1u) != 0;
-#endif
-                bool sdy = false;
-                if (STEADY) sdy = steady_iter<EXIT>(P, c, we, st, ct);
-                if (st == 0u && !sdy) {
-                    shd_event e;
-#ifdef SHD_TIMING_INLOOP
-                    const unsigned long long q0 = wall_clock64();
-#endif
-                    const bool got = take_next(P, c, we, e);
-#ifdef SHD_TIMING_INLOOP
-                    const unsigned long long q1 = wall_clock64();
-                    t_q[0] += q1 - q0;
-#endif
-                    if (got) {
-                        c.now = e.time;
-                        begin_event<HR>(P, c, e);
-#ifdef SHD_TIMING_INLOOP
-                        t_q[1] += wall_clock64() - q1;
-#endif
-                        st = ((c.w_fl & ~W_READ) | c.w_msgs) ? 1u : 0u;
-#ifndef SHD_NO_FUSE
-#ifdef SHD_TIMING_INLOOP
-                        const unsigned long long q2 = wall_clock64();
-#endif
-                        if (st == 0u && c.tt2 < we) {   // the notification, when it is next (round_body)
-                            const uint64_t t = c.tt2, ht = c.evq_n ? c.top_time : kInf;
-                            if (t < c.tt0 && t < c.tt1 && t < c.dt && t < ht && notify_fast_ok<HR>(P, c)) {
-                                c.tt2 = kInf; c.now = t; c.c_events++;
-                                c.q_seq = c.ts2; c.q_src = c.h; c.q_sub = 0;
-                                c.w_msgs = 0; c.w_fl = 0;
-                                notify_fast(P, c);
-                                st = c.w_fl ? 1u : 0u;
-                            }
-                        }
-#ifdef SHD_TIMING_INLOOP
-                        t_q[2] += wall_clock64() - q2;
-#endif
-                        if (st == 0u && c.tt1 < we) {   // the periodic refill, when it is next
-                            const uint64_t t = c.tt1, ht = c.evq_n ? c.top_time : kInf;
-                            if (t < c.tt0 && t < c.tt2 && t < c.dt && t < ht && c.cq_count == 0 && c.tq_count == 0) {
-                                c.tt1 = kInf; c.now = t; c.c_events++;
-                                c.q_seq = c.ts1; c.q_src = c.h; c.q_sub = 0;
-                                c.w_msgs = 0; c.w_fl = 0;
-                                refill_fast(P, c);
-                            }
-                        }
-#endif
-                    } else {
-                        st = 3u;
-                    }
-                }
-#ifdef SHD_TIMING_INLOOP
-                {
-                    const unsigned long long tb = wall_clock64();
-                    t_take += tb - ta;
-                    ta = tb;
-                }
-#endif
-                if (st == 1u) st = run_work<HR>(P, c) ? 0u : 2u;
-#ifdef SHD_TIMING_INLOOP
-                t_work += wall_clock64() - ta;
-#endif
-                if (EXIT && st == 0u) {
-                    ct = next_cand(c);
-                    if (ct >= we) st = 3u;
-                }
-#ifdef SHD_TIMING_EXIT
-                // the pass in which no lane ran an event or worked (the parent's last one)
-                t_empty = (!work && __ballot(c.c_events != ev0) == 0) ? wall_clock64() - tx : 0;
-#endif
-                if (__ballot(st <= 1u) == 0) break;
-            }
-            const bool last = __ballot(st == 2u) == 0;
-#ifdef SHD_TIMING
-            if (last) TIMP(3);   // the round's last flush starts
-#endif
-#ifdef SHD_TIMING_LIGHT
-            n_fl++;
-#endif
-#ifdef SHD_TIMING_INLOOP
-            ta = wall_clock64();
-#endif
-            // PF: the round's last flush, when it is one batch, is taken below,
-            // in two steps around the close; of more than one batch: here,
-            // whole (not deferred: its deliveries go out with it)
-            if (PF && last) {
-                total = flush_total();
-                if (total <= (uint32_t)kBlock) break;
-                total = 0;
-            }
-            flush_wave<true, XCH>(P, c, !PF && last, pd);
-#ifdef SHD_TIMING_INLOOP
-            if (!last) t_fl += wall_clock64() - ta;
-#endif
-            if (last) break;
-            if (st == 2u) st = 1u;
-        }
-    }
-    const auto loop_done = [&]() {
-        TIMP(4);
-#ifdef SHD_TIMING_LIGHT
-        TIMVP(16, (uint64_t)n_it);   // loop iterations of the wave
-        TIMVP(17, (uint64_t)n_fl);   // flushes
-        TIMVP(18, (uint64_t)__popcll(__ballot(active)));
-#ifdef SHD_TIMING_EXIT
-        TIMVP(8, t_empty + 1);   // the loop's last pass when no lane ran an event or worked in it (+ 1; 1: it did)
-#else
-        TIMVP(8, t_take);    // in take_next + begin_event (+ the fused notification / refill)
-#endif
-#if !defined(SHD_TIMING_EXIT) && !defined(SHD_TIMING_CARRY)   // (SHD_TIMING_CARRY, a NOLOOP build: slot 9 is the last flush's kinds)
-        TIMVP(9, t_work);    // in run_work
-#endif
-        TIMVP(10, t_fl);     // in the flushes before the last
-        TIMVP(11, t_q[0]);   // of 8: take_next
-        TIMVP(15, t_q[1]);   //       begin_event
-        TIMVP(19, t_q[2]);   //       the fused notification (the rest: the fused refill, the loop's own)
-#endif
-    };
-    // PF (k_round_ps): the last flush's path loads go out first and the close
-    // runs while they are in flight: it needs nothing of the flush but
-    // min_emit, and the flush nothing of it (pf_lim is the round's).  The next
-    // window's bins may so be loaded ahead of this wave's own deliveries into
-    // them: those are noted as every other block's (note_dirty in
-    // flush_finish, before ps_noted reads the list), and a noted host reads
-    // its window again.  The prefetch loads follow the path loads (ahead of
-    // them they delay the resolve by their own round trip: loads return in
-    // order), and are countable (pf_issue), so the resolve waits for the path
-    // loads alone.
-    // Not PF (k_round_sp's passes: a few sends each and next to no close to put
-    // under them; the split measured 2 % slower there): the last flush's stores,
-    // then the close.
+template <class Fin>
+__device__ __forceinline__ void ps_close_pf(const DParams& P, HostCtx& c, bool active, bool has, const PsRsrc& R,
+                                            uint32_t lb, uint64_t we, uint32_t (&w)[kNBW], uint32_t clr_p,
+                                            uint32_t clr, uint64_t& next, PfBins& pb, uint64_t& span, uint32_t total,
+                                            PsLoopEnd& le, const Fin& fin, PsCarry& cy) {
+    PendDel& pd = le.pd;   // (empty so far: the loop's own flushes were whole, LASTOUT)
     LastFlush lf;
-    if (PF) {
-        if (total) flush_last_issue(P, c, total, lf);
-    } else {
-        loop_done();
-        flush_finish<XCH>(P, c, pd);
-    }
-    uint64_t sp = 0;
-    if (PF) {
-        bm_clear(w, clr_p, clr);
-        const uint64_t b1 = we >> P.bin_shift;
-        sp = bm_span(w, (uint32_t)b1 & (kNB - 1));
-        *span = sp;
-        pf_issue(R, lb, b1, sp, has, *pb);
-    }
+    if (total) flush_last_issue(P, c, total, lf);
+    bm_clear(w, clr_p, clr);
+    const uint64_t b1 = we >> P.bin_shift;
+    const uint64_t sp = bm_span(w, (uint32_t)b1 & (kNB - 1));
+    span = sp;
+    pf_issue(R, lb, b1, sp, has, pb);
     if (has) {   // (an idle lane's from its timers and bitmap; the consumed bins were cleared in w)
         next = host_next(c);
         if (P.bins) {
-            const uint64_t cb = cal_lower_bound_sp<PF>(P, w, sp, we);
+            const uint64_t cb = cal_lower_bound_sp(P, w, sp, we);
             next = cb < next ? cb : next;
         }
     }
     fin();
-    if (PF) {
-#ifdef SHD_TIMING_LIGHT
-        TIMP(23);   // the close's work under the path loads done: their wait is next (k_round_sp: 23 is its own)
-#endif
-        if (total) flush_last_consume<true>(P, c, lf, pd);
-        loop_done();
-        // the stores wait for the calendar claims alone; a delivery into a
-        // bin loaded ahead is noted here
-        if (CARRY) {
-            if (active && c.min_emit < next) next = c.min_emit;
-            uint64_t n = wave_min_u64(next);
-            n = cy->carry < n ? cy->carry : n;
-            next = n;
-            uint64_t lim = n + cy->window;
-            if (lim > cy->stop || lim < n) lim = cy->stop;
-            cy->far_t = flush_finish_far<XCH>(P, c, pd, (lim >> P.bin_shift) + kPfBins, cy->any);
-#ifdef SHD_TIMING_CARRY   // 1 + (the last flush had a near delivery) + 2 x (a far one)
-            TIMVP(9, 1ull + (__ballot(pd.kind != 0 && cy->far_t == kInf) != 0 ? 1u : 0u) + (cy->any ? 2u : 0u));
-#endif
-        } else {
-#ifdef SHD_TIMING_CARRY   // the same under the rule, for a build without it (k_round_ps: cy is given)
-            if (cy) {
-                uint64_t n = next;
-                if (active && c.min_emit < n) n = c.min_emit;
-                n = wave_min_u64(n);
-                uint64_t lim = n + cy->window;
-                if (lim > cy->stop || lim < n) lim = cy->stop;
-                const bool far = pd.kind == 1 && pd.slot < kBinCap && !pd.near &&
-                                 (s_res[threadIdx.x].time >> P.bin_shift) >= (lim >> P.bin_shift) + kPfBins;
-                TIMVP(9, 1ull + (__ballot(pd.kind != 0 && !far) != 0 ? 1u : 0u) + (__ballot(far) != 0 ? 2u : 0u));
-            }
-#endif
-            flush_finish<XCH>(P, c, pd);
-        }
-#ifdef SHD_TIMING_LIGHT
-        TIMP(21);   // the claims are back, the last flush's stores issued (k_round_sp: 20, 21 are its own)
-#endif
-    }
-    if (!CARRY && active && c.min_emit < next) next = c.min_emit;
+    TIMPL(23);   // the close's work under the path loads done: their wait is next (k_round_sp: 23 is its own)
+    if (total) flush_last_consume<true>(P, c, lf, pd);
+    le.tm.done(P, active);
+    // the stores wait for the calendar claims alone; a delivery into a bin
+    // loaded ahead is noted here
+    if (active && c.min_emit < next) next = c.min_emit;
+    uint64_t n = wave_min_u64(next);
+    n = cy.carry < n ? cy.carry : n;
+    next = n;
+    uint64_t lim = n + cy.window;
+    if (lim > cy.stop || lim < n) lim = cy.stop;
+    cy.far_t = flush_finish_far<false>(P, c, pd, (lim >> P.bin_shift) + kPfBins, cy.any);
+    TIMPL(21);   // the claims are back, the last flush's stores issued (k_round_sp: 20, 21 are its own)
     TIMP(5);
 }
 
-// k_round_sp's round of an active host (ps_prologue + ps_loop_close)
+// k_round_ps's loop and close, with what the loop hands to the close in one
+// frame (why not in the kernel's own round loop: profiles/psloop/INDEX.md)
+template <bool LEAN, class Fin>
+__device__ __forceinline__ void ps_loop_close_pf(const DParams& P, HostCtx& c, bool active, bool has, const PsRsrc& R,
+                                                 uint32_t lb, uint64_t we, uint32_t (&w)[kNBW], uint32_t clr_p,
+                                                 uint32_t clr, uint64_t& next, PfBins& pb, uint64_t& span,
+                                                 const Fin& fin, PsCarry& cy) {
+    PsLoopEnd le;
+    const uint32_t total = ps_loop<true, LEAN, false, !LEAN>(P, c, active, we, le);
+    ps_close_pf(P, c, active, has, R, lb, we, w, clr_p, clr, next, pb, span, total, le, fin, cy);
+}
+
+// k_round_sp's round of an active host (ps_prologue, ps_loop, ps_close)
 template <bool SP, bool XCH = true, bool HR = true>
 __device__ __forceinline__ void ps_round_body(const DParams& P, HostCtx& c, bool active, uint32_t lb, const PsRsrc& R,
                                               uint64_t ws, uint64_t we, int parity, uint32_t nin,
                                               uint32_t (&w)[kNBW], uint32_t wbits, uint64_t& next,
                                               const SpIn* sp = nullptr) {
     ps_prologue<SP>(P, c, active, lb, R, ws, we, parity, nin, w, wbits, sp);
-    ps_loop_close<false, XCH, PsNoFin, false, false, false, HR>(P, c, active, active, R, lb, we, w, 0u, 0u, next, nullptr,
-                                                                nullptr);
+    PsLoopEnd le;
+    ps_loop<false, false, XCH, HR>(P, c, active, we, le);
+    ps_close<XCH>(P, c, active, we, w, next, le);
 }
 
 // The shares' granules are stored in three planes (round 6): granule g of slot
 // s at (g * nsl + s) * 16, nsl = the slots of both parities -- so a wave's poll
 // of 64 blocks' first granules reads 1 KB of consecutive lines instead of 64
 // sectors 48 B apart (every block polls every share every round: at the C5
-// shard 489 x 489 of them); SHD_PS_AOS keeps the 48-B records for an A/B
-#ifdef SHD_PS_AOS
-__device__ __forceinline__ uint32_t ps_goff(uint32_t nsl, uint32_t slot, uint32_t g) { return slot * 48u + g * 16u; }
-#else
+// shard 489 x 489 of them)
 __device__ __forceinline__ uint32_t ps_goff(uint32_t nsl, uint32_t slot, uint32_t g) { return (g * nsl + slot) * 16u; }
-#endif
 // the share of round i: its three granules tagged, stored write-through after
 // the wave's hand-off stores drained; d: the noted destinations.
-// CARRY and `far` (wave-uniform): the wave's kFarVm youngest vector-memory
+// `far` (k_round_ps; wave-uniform): the wave's kFarVm youngest vector-memory
 // instructions are its far group (flush_finish_far), which stays in flight:
 // vector-memory operations complete in issue order, so everything older has
 // landed, and an instruction issued behind the group only makes the wait
 // longer.  The next share's wait takes the group in, being older than it
-template <bool CARRY = false>
 __device__ __forceinline__ void ps_publish(__amdgpu_buffer_rsrc_t rs, uint32_t nsl, uint32_t slot, uint64_t next,
                                            uint32_t flags, uint32_t nev, uint32_t npkt, uint32_t nact, uint32_t tag,
                                            uint4 d, bool far = false) {
     static_assert(kFarVm == 3, "the waits below name the far group's size");
 #if defined(SHD_TIMING_LIGHT) && defined(SHD_TIMING_NOWAIT)
     // the timing build's stamps between the far group and here are stores of their own, issued by
-    // every block below 2048 (stamps 21 and 5, and slot 9 of a SHD_TIMING_CARRY build): counted in,
-    // so that the stamps show the product's wait
-#ifdef SHD_TIMING_CARRY
-    if (CARRY && far && blockIdx.x < 2048) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-#else
-    if (CARRY && far && blockIdx.x < 2048) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-#endif
+    // every block below 2048 (stamps 21 and 5): counted in, so that the stamps show the product's wait
+    if (far && blockIdx.x < 2048) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #else
-    if (CARRY && far) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");   // every store before the far group has landed
+    if (far) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");   // every store before the far group has landed
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every store of this wave has landed
 #endif
     if (threadIdx.x == 0) {
@@ -1757,7 +1729,7 @@ __device__ __forceinline__ void ps_fresh(DevSummary* s) {
 // Pr[i + 1] differ in `sum` only, and a copy per round made every round's
 // first read of each field a scalar-cache miss; the round's summary is
 // s_rsum.  (Timing builds keep the copy per round: the stamps' slot follows
-// P.sum.  SHD_PS_PR: the same, for an A/B.)
+// P.sum.)
 #if defined(SHD_TIMING_P0)
 #define PS_PARAMS(i)                                                                          \
     const DParams& P = P0;                                                                    \
@@ -1765,7 +1737,7 @@ __device__ __forceinline__ void ps_fresh(DevSummary* s) {
         s_rsum = &ring[(i) + 1];                                                              \
         s_tslot = (uint32_t)(((uintptr_t)&ring[(i) + 1] / sizeof(DevSummary)) & 63);          \
     }
-#elif defined(SHD_TIMING) || defined(SHD_PS_PR)
+#elif defined(SHD_TIMING)
 #define PS_PARAMS(i)                                    \
     const DParams& P = Pr[(i) + 1];                     \
     if (threadIdx.x == 0) s_rsum = &ring[(i) + 1]
@@ -1775,41 +1747,9 @@ __device__ __forceinline__ void ps_fresh(DevSummary* s) {
     if (threadIdx.x == 0) s_rsum = &ring[(i) + 1]
 #endif
 
-
-#ifndef SHD_NO_PF
-constexpr bool kPsPf = true;
-#else
-constexpr bool kPsPf = false;
-#endif
-
-#ifndef SHD_NO_STEADY
-constexpr bool kPsSteady = true;
-#else
-constexpr bool kPsSteady = false;
-#endif
-
-// the event loop's two ends (the lean k_round_ps): the loop leaves with its
-// last event (ps_loop_close's EXIT), and the fast round takes its due count
-// and head from the staging (pf_stage, ps_prologue_pf); SHD_NO_EXIT1 /
-// SHD_NO_EXIT2 build the loop and the scan as they were, for an A/B
-#ifndef SHD_NO_EXIT1
-constexpr bool kPsExit = true;
-#else
-constexpr bool kPsExit = false;
-#endif
-#ifndef SHD_NO_EXIT2
-constexpr bool kPsDueAhead = true;
-#else
-constexpr bool kPsDueAhead = false;
-#endif
-// the last flush's far deliveries complete behind the share (ps_loop_close's
-// CARRY); SHD_NO_CARRY builds the round without it, for an A/B
-#ifndef SHD_NO_CARRY
-constexpr bool kPsCarry = kPsPf;
-#else
-constexpr bool kPsCarry = false;
-#endif
-
+// (the lean kernel's event loop has two ends of its own: it leaves with its
+// last event -- ps_loop's STEADY -- and the fast round takes its due count and
+// head from the staging: pf_stage, ps_prologue_pf)
 template <bool LEAN>
 __global__ __launch_bounds__(kBlock) void k_round_ps(uint64_t window, int nb, DevSummary* __restrict__ ring,
                                                       const DevCtl* __restrict__ ctl, PsShare* __restrict__ shares,
@@ -1852,13 +1792,13 @@ __global__ __launch_bounds__(kBlock) void k_round_ps(uint64_t window, int nb, De
     // dirty): valid, its first bin, the due events staged (kDueCap + 1:
     // overflow), the span from that bin on of that round's close bitmap
     // (bm_span: the next window's bits), named by a share
-    const bool pfm = kPsPf && P0.bins != nullptr;
+    const bool pfm = P0.bins != nullptr;
     bool pf = false;
     uint64_t pf_b0 = 0;
     uint32_t pnd = 0, dirty = 0;
     uint64_t pspan = 0;
-    PfDue pdu{0, kInf, kInf};   // LEAN && kPsDueAhead: what pf_stage knows of the next window's due list
-    PsCarry cy{window, stop, kInf, kInf, false};   // kPsCarry: the far deliveries' bound, from a round to the next
+    PfDue pdu{0, kInf, kInf};   // LEAN: what pf_stage knows of the next window's due list
+    PsCarry cy{window, stop, kInf, kInf, false};   // the far deliveries' bound, from a round to the next
     for (int i = 0; i < nb; i++) {
         PS_PARAMS(i);
         const unsigned long long t_start = wall_clock64();
@@ -1889,7 +1829,7 @@ __global__ __launch_bounds__(kBlock) void k_round_ps(uint64_t window, int nb, De
             const uint32_t wbits = ps_window_bits(P, c, pspan, (uint32_t)((ws >> P.bin_shift) - pf_b0), ws, we);
             TIMP(1);
             active = has && !(host_next(c) >= we && wbits == 0);   // (no inbox: it would have been named)
-            ps_prologue_pf<LEAN && kPsDueAhead>(P, c, active, ws, we, pnd, pdu, wbits, clr);
+            ps_prologue_pf<LEAN>(P, c, active, ws, we, pnd, pdu, wbits, clr);
         } else {
             // the round's hand-off words: this parity's inbox count, the calendar bitmap
             uint32_t nin = 0;
@@ -1917,17 +1857,17 @@ __global__ __launch_bounds__(kBlock) void k_round_ps(uint64_t window, int nb, De
             nev = wave_sum_u32(c.c_events);
             npkt = wave_sum_u32(c.c_pkt);
         };
-        ps_loop_close<kPsPf, false, decltype(fin), LEAN && kPsSteady, LEAN && kPsSteady && kPsExit, kPsCarry, !LEAN>(
-            P, c, active, has, R, lb, we, w, (uint32_t)(ws >> P.bin_shift) & (kNB - 1), clr, next, &pb, &span, fin, &cy);
+        ps_loop_close_pf<LEAN>(P, c, active, has, R, lb, we, w, (uint32_t)(ws >> P.bin_shift) & (kNB - 1), clr, next, pb,
+                               span, fin, cy);
         acc[2] += c.c_sent; acc[3] += c.c_idrop;
         const uint32_t pend = c.n_pend ? kPsPend : 0u;
         const uint32_t fl = wave_or_u32(c.err | pend);
-        if (!kPsCarry) next = wave_min_u64(next);   // (kPsCarry: folded ahead of the stores)
         const uint32_t tag = tag0 + (uint32_t)i;
         const uint32_t base = (uint32_t)(i & 1) * nblk;
-        ps_publish<kPsCarry>(rs, 2 * nblk, base + blockIdx.x, next, fl, nev, npkt, nact, tag, ps_noted(pfm), cy.any);
+        // (next: the block's, folded ahead of the last flush's stores, ps_close_pf)
+        ps_publish(rs, 2 * nblk, base + blockIdx.x, next, fl, nev, npkt, nact, tag, ps_noted(pfm), cy.any);
         TIMP(6);
-        if (kPsCarry) {   // the far deliveries' bound for the next share, folded behind this one
+        {   // the far deliveries' bound for the next share, folded behind this one
             const uint64_t t = wave_min_u64(cy.far_t);
             cy.carry = t == kInf ? kInf : (t >> P.bin_shift) << P.bin_shift;
         }
@@ -1937,7 +1877,7 @@ __global__ __launch_bounds__(kBlock) void k_round_ps(uint64_t window, int nb, De
             // min(f_next + window, stop) and f_next >= we (the same clip as `we`)
             uint64_t lim = we + window;
             if (lim > stop || lim < we) lim = stop;
-            pnd = pf_stage<LEAN && kPsDueAhead>(pb, we, (b1 + kPfBins) << P.bin_shift, lim, pdu);
+            pnd = pf_stage<LEAN>(pb, we, (b1 + kPfBins) << P.bin_shift, lim, pdu);
             pf_b0 = b1;
             pspan = span;
         }
@@ -1946,12 +1886,12 @@ __global__ __launch_bounds__(kBlock) void k_round_ps(uint64_t window, int nb, De
         bool dall = false;
 #ifdef SHD_TIMING_LIGHT
         uint32_t n_poll = 0;
-        const bool ok_v = ps_gather<kPsPf>(rs, 2 * nblk, base, nblk, tag, blockIdx.x == 0, ticks, f_next, f_fl, f_nev, f_npkt,
-                                           f_nact, hb, (uint32_t)P.hpw, &dm, &dall, &n_poll);
+        const bool ok_v = ps_gather<true>(rs, 2 * nblk, base, nblk, tag, blockIdx.x == 0, ticks, f_next, f_fl, f_nev, f_npkt,
+                                          f_nact, hb, (uint32_t)P.hpw, &dm, &dall, &n_poll);
         TIMVP(22, (uint64_t)n_poll);   // the gather's poll passes (k_round_sp: 22 is its own)
 #else
-        const bool ok_v = ps_gather<kPsPf>(rs, 2 * nblk, base, nblk, tag, blockIdx.x == 0, ticks, f_next, f_fl, f_nev, f_npkt,
-                                           f_nact, hb, (uint32_t)P.hpw, &dm, &dall);
+        const bool ok_v = ps_gather<true>(rs, 2 * nblk, base, nblk, tag, blockIdx.x == 0, ticks, f_next, f_fl, f_nev, f_npkt,
+                                          f_nact, hb, (uint32_t)P.hpw, &dm, &dall);
 #endif
         TIMP(7);
         // the folds come out of ps_gather in scalar registers, so the round
@@ -1983,9 +1923,7 @@ __global__ __launch_bounds__(kBlock) void k_round_ps(uint64_t window, int nb, De
         if (ws >= stop) break;      // the rest only forwards the time (ring[i + 1].next_time says so)
         pf = pfm;
         dirty = (dall || ((dm >> lb) & 1ull)) ? 1u : 0u;
-#ifdef SHD_TIMING_LIGHT
-        TIMP(20);   // the round's end: the summary and the exit tests behind the gather (k_round_sp: 20 is its own)
-#endif
+        TIMPL(20);   // the round's end: the summary and the exit tests behind the gather (k_round_sp: 20 is its own)
     }
     // the hosts' state, once for the whole batch
     if (has) {
