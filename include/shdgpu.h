@@ -332,7 +332,8 @@ typedef struct shd_model {
     const struct shd_udp_app* app_spec;   /* [n_app_specs] (SHD_APP_UDP) or NULL */
     const uint8_t* host_app;        /* [H] (SHD_APP_UDP) or NULL               */
     uint32_t n_app_specs;           /* <= 256                                  */
-    uint32_t _pad3;
+    uint32_t hostrec_interval_us;   /* SHD_QF_HOST_SERIES: the sampling interval in us (boundaries at
+                                       k x 1000 x this ns, k >= 1, before end_time); ignored without the flag */
 } shd_model;
 
 enum { SHD_APP_PHOLD = 0, SHD_APP_UDP_ECHO = 1, SHD_APP_UDP = 2 };
@@ -384,7 +385,14 @@ enum { SHD_QF_NO_CALENDAR = 1,
         * queue and its interface did, counted on the device where the reference
         * raises the packet statuses, in an untraced run as well (read with
         * shd_eng_host_records) */
-       SHD_QF_HOST_RECORDS = 32 };
+       SHD_QF_HOST_RECORDS = 32,
+       /* with SHD_QF_HOST_RECORDS and a nonzero shd_model.hostrec_interval_us:
+        * one sample of a host's record for every interval in which the record
+        * was touched (struct shd_host_sample, shdtcp.h; read with
+        * shd_eng_host_series).  shd_eng_create refuses (SHD_EINVAL, before any
+        * device call) the flag without the records flag, with a zero interval,
+        * or with end_time / interval >= 2^32 */
+       SHD_QF_HOST_SERIES = 64 };
 
 /* one event (32 B): key (time, dst, src, seq) = event_compare, event.c:110-153 */
 typedef struct shd_event {
@@ -474,6 +482,9 @@ enum {
     SHD_ERR_EVQ_OVERFLOW = 1, SHD_ERR_INBOX_OVERFLOW = 2, SHD_ERR_CODELQ_OVERFLOW = 4,
     SHD_ERR_TXQ_OVERFLOW = 8, SHD_ERR_AMBIGUOUS = 16, SHD_ERR_PENDING_OVERFLOW = 32,
     SHD_ERR_TRACE_OVERFLOW = 64, SHD_ERR_REMOTE_OVERFLOW = 128,
+    SHD_ERR_HOST_SERIES = 256,      /* SHD_QF_HOST_SERIES: an append found the sample array full and wrote
+                                       nothing (host-driven rounds only: the run calls stop and empty the
+                                       array often enough by construction) */
     SHD_ERR_INTERNAL = 0x80000000u  /* engine invariant broken (bad event kind, timer slot reuse) */
 };
 
@@ -648,6 +659,37 @@ int shd_eng_heartbeats(shd_eng* e, uint32_t* out, uint64_t cap, uint64_t* n);
  * array.  *n = host_end - host_begin; SHD_ERANGE if cap < *n. */
 struct shd_tcp_hostrec;
 int shd_eng_host_records(shd_eng* e, struct shd_tcp_hostrec* out, uint64_t cap, uint64_t* n);
+/* the host records' series (model queue_flags & SHD_QF_HOST_SERIES; SHD_EINVAL
+ * without).  With I = 1000 * hostrec_interval_us ns the boundaries are T_k = k I,
+ * k >= 1, T_k < end_time.  A record is touched when one of the statuses it
+ * counts is raised on its host; a touched record yields one sample labelled
+ * with the first boundary after the touch (a touch at exactly T_k belongs to
+ * the interval after it), and the sample is the whole record as it stood after
+ * every event of the host before that boundary, depth_end the queue's length
+ * at the boundary.  An interval without a touch has no sample (the reader
+ * fills forward); a last touch whose boundary is not before end_time has none
+ * either: shd_eng_host_records is that point.
+ * out = every sample with T <= the time up to which the engine has run (the
+ * stop of the last completed shd_eng_run / shd_eng_run_until /
+ * shd_xgroup_run_until, or the window end of the last host-driven round) and
+ * T < end_time, sorted by (host, t); host, depth_end and the byte fields are
+ * filled in as shd_eng_host_records fills them.  So a read after a step
+ * returns the full run's rows with T <= that step's stop.  Callable after any
+ * run call, any number of times: it reads and resets nothing; a rolled-back or
+ * replayed round samples once.  The run calls stop at every q-th boundary (q =
+ * max(1, capacity / local hosts); capacity max(2^18, 2 x local hosts) samples,
+ * or SHD_HOST_SERIES_CAP in the environment, SHD_EINVAL below the local hosts)
+ * and empty the device's sample array there, so it cannot fill; host-driven
+ * rounds empty it at every shd_eng_end_round, and a round that fills it sets
+ * SHD_ERR_HOST_SERIES.  In a group every engine returns its own hosts'
+ * samples.  *n = the samples; SHD_ERANGE if cap < *n. */
+struct shd_host_sample;
+int shd_eng_host_series(shd_eng* e, struct shd_host_sample* out, uint64_t cap, uint64_t* n);
+/* what the series cost so far: out[0] samples taken off the device, out[1] the
+ * times the array was emptied with something in it, out[2] the most it held
+ * then, out[3] its capacity, out[4] the stops the run calls added at
+ * boundaries (chunks).  SHD_EINVAL without the flag. */
+int shd_eng_host_series_info(shd_eng* e, uint64_t out[5]);
 
 /* ---- the reference's log lines, made by the library ----
  * A set of lines: line i is text[off[i] .. off[i+1]) (no newline; text is

@@ -452,6 +452,19 @@ typedef struct shd_tcp_hostrec {
     uint32_t sojourn_hist[16];
 } shd_tcp_hostrec;
 
+/* One sample of a host-record series (the packet engine's SHD_QF_HOST_SERIES,
+ * shdgpu.h shd_eng_host_series): `rec` is host rec.host's whole record as it
+ * stood after every event of the host before the boundary `t` (ns, a multiple
+ * of the interval), depth_end the queue's length at `t`.  A host has a sample
+ * for boundary t only if one of the record's statuses was raised on it in the
+ * interval that ends at t (an event at exactly t belongs to the next one), so
+ * a reader fills forward: the record at an unsampled boundary is the host's
+ * last sample before it, and zero before its first. */
+typedef struct shd_host_sample {
+    uint64_t t;
+    shd_tcp_hostrec rec;
+} shd_host_sample;   /* 240 B */
+
 /* shd_tcp_model.options: independent bits, but SHD_TCP_OPT_SERIES is valid only
  * together with SHD_TCP_OPT_FLOWS and a nonzero series_interval_us (-22
  * otherwise, before any device call) */

@@ -229,7 +229,19 @@ constexpr int kDestExc = 16;   // closed-form destination exceptions (ParamsT::e
 // ParamsT::feat: the model's optional features (all off on the bench's models)
 constexpr uint32_t F_TRACE = 1u, F_HB = 2u, F_PCOUNT = 4u, F_HOSTHB = 8u, F_AMBIG = 16u, F_STATUS = 64u,
                    F_APP = 128u,    // the application is not PHOLD: per-host modes (app_send / app_dest)
-                   F_HOSTREC = 32u; // SHD_QF_HOST_RECORDS: per-host router-queue / interface records (ParamsT::hrec)
+                   F_HOSTREC = 32u, // SHD_QF_HOST_RECORDS: per-host router-queue / interface records (ParamsT::hrec)
+                   F_HOSTSER = 256u; // SHD_QF_HOST_SERIES: a sample of the record per touched interval (ParamsT::hser)
+
+// the host-record series' control block (SHD_QF_HOST_SERIES; one per engine, device memory
+// outside the engine's allocation list: a state copy holds neither it nor the samples)
+struct HserCtl {
+    shd_host_sample* buf;         // [cap] samples appended since the host last emptied it
+    unsigned long long n;         // places handed out (atomicAdd; past cap: nothing was written)
+    unsigned long long cap;
+    unsigned long long interval;  // I, ns
+    uint32_t full;                // an append found buf full (SHD_ERR_HOST_SERIES)
+    uint32_t pad;
+};
 
 template <template <class> class Ptr>
 struct ParamsT {
@@ -339,6 +351,8 @@ struct ParamsT {
     // host, written by the host's own lane alone (hrec_count).  Last, so that every
     // other field keeps its place in the kernels' argument block
     Ptr<shd_tcp_hostrec> hrec;         // [nloc]
+    // the records' per-interval series (SHD_QF_HOST_SERIES: F_HOSTSER), else null
+    Ptr<HserCtl> hser;
 };
 // The host fills Params (plain pointers); device code reads the same bytes
 // as DParams, whose pointers carry the global address space, so that loads
@@ -738,7 +752,36 @@ enum : uint32_t { HR_ENQUEUED, HR_DEQUEUED, HR_DROPPED, HR_IF_RECEIVED, HR_IF_DR
 // right after, this packet included; HR_DEQUEUED the packet's enqueue time.
 // One body for all the count points, called: inlined at each of them it is a
 // few hundred instructions more in kernels that have no registers to spare.
-__device__ __noinline__ void hrec_count(GlobalPtr<shd_tcp_hostrec> r, uint64_t now, uint32_t what, uint64_t arg) {
+//
+// The series (SHD_QF_HOST_SERIES, hs != null) is sampled lazily, here alone.
+// A host's pending boundary is the first boundary T_k = k I after its last
+// touch, kept as k in the record's _pad word (0: none; `host` and `_pad` are
+// dead on the device otherwise, `host` holds the model's host index for the
+// sample's reader).  The first count at or past T_k appends {T_k, record}
+// BEFORE it counts: only counts change a record, so that is the record after
+// every event before T_k.  The place comes from one engine-wide counter; a
+// full array takes nothing and raises HserCtl::full.  The division runs on an
+// interval's first touch only.
+__device__ __noinline__ void hrec_count(GlobalPtr<shd_tcp_hostrec> r, GlobalPtr<HserCtl> hs, uint64_t now,
+                                        uint32_t what, uint64_t arg) {
+    if (hs) {
+        const uint64_t I = hs->interval;
+        uint32_t k = r->_pad;
+        if (k && now >= (uint64_t)k * I) {
+            const unsigned long long i = atomicAdd(&hs->n, 1ull);
+            if (i < hs->cap) {
+                GlobalPtr<uint64_t> d = (GlobalPtr<uint64_t>)(hs->buf + i);
+                GlobalPtr<const uint64_t> q = (GlobalPtr<const uint64_t>)r;
+                d[0] = (uint64_t)k * I;
+#pragma unroll
+                for (uint32_t j = 0; j < sizeof(shd_tcp_hostrec) / 8; j++) d[1 + j] = q[j];
+            } else {
+                hs->full = 1u;
+            }
+            k = 0;
+        }
+        if (!k) r->_pad = (uint32_t)(now / I) + 1u;
+    }
     if (!r->t_first) r->t_first = now;
     r->t_last = now;
     switch (what) {
@@ -772,7 +815,7 @@ template <bool HR>
 __device__ __forceinline__ bool hrec_on(const HostCtx& c) { return HR && (c.k.feat & F_HOSTREC) != 0; }
 template <bool HR>
 __device__ __forceinline__ void hrec(const DParams& P, const HostCtx& c, uint32_t what, uint64_t arg = 0) {
-    if (HR && (c.k.feat & F_HOSTREC)) hrec_count(P.hrec + c.l, c.now, what, arg);
+    if (HR && (c.k.feat & F_HOSTREC)) hrec_count(P.hrec + c.l, P.hser, c.now, what, arg);
 }
 
 // the tracker interval of host h (<host heartbeatfrequency>, host.c:240; the

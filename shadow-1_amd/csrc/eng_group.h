@@ -820,7 +820,43 @@ static int x_launch_rounds(shd_xgroup* g, int nb) {
     return SHD_OK;
 }
 
+static int x_run_until_one(shd_xgroup* g, uint64_t t_stop, shd_run_stats* st);
+// With the host records' series the group advances in the chunks of
+// shd_eng_run_until: every rank computes the same stops from the model and the
+// last stop alone, and nothing is exchanged -- each engine keeps its own hosts'
+// samples.  Without the flag: one call, unchanged.
 extern "C" int shd_xgroup_run_until(shd_xgroup* g, uint64_t t_stop, shd_run_stats* st) {
+    if (!g) return SHD_EINVAL;
+    if (g->engs.empty() || !g->engs[0]->d_hser) return x_run_until_one(g, t_stop, st);
+    shd_eng* e0 = g->engs[0];
+    const uint64_t stop = std::min<uint64_t>(t_stop, g->end_time);
+    // boundaries per chunk: the least of the ranks' capacity / hosts, over the
+    // group's partition b[p] = (H p) / world (every rank's capacity follows
+    // from its hosts, or is the environment's for all)
+    uint64_t q = ~0ull;
+    for (uint64_t p = 0, H = (uint64_t)e0->H, N = (uint64_t)g->world; p < N; p++) {
+        const uint64_t nl = H * (p + 1) / N - H * p / N;
+        const uint64_t cap = e0->hser_cap_env ? e0->hser_cap : std::max<uint64_t>(1ull << 18, 2 * nl);
+        if (nl) q = std::min(q, std::max<uint64_t>(1, cap / nl));
+    }
+    for (const shd_eng* e : g->engs) q = std::min(q, e->hser_q);   // (a local group of any partition)
+    shd_run_stats tot{};
+    uint64_t from = e0->t_done;
+    int rc;
+    do {
+        const uint64_t cs = hser_chunk_stop(e0, from, stop, q);
+        if (cs < stop)
+            for (shd_eng* e : g->engs) e->hser_chunks++;
+        shd_run_stats s{};
+        rc = x_run_until_one(g, cs, &s);
+        add_stats(tot, s);
+        from = std::max(from, cs);
+    } while (rc == SHD_OK && from < stop);
+    if (st) *st = tot;
+    return rc;
+}
+
+static int x_run_until_one(shd_xgroup* g, uint64_t t_stop, shd_run_stats* st) {
     if (!g) return SHD_EINVAL;
     auto t0 = std::chrono::steady_clock::now();
     const int nl = (int)g->engs.size();
@@ -1081,6 +1117,15 @@ extern "C" int shd_xgroup_run_until(shd_xgroup* g, uint64_t t_stop, shd_run_stat
     for (int k = 0; k < nl; k++) {
         shd_eng* e = g->engs[k];
         e->h_sum->next_time = g->next;
+        if (e->d_hser) {   // the series: every engine's samples, the array empty between run calls
+            (void)hipSetDevice(e->device);
+            const int rc1 = hser_drain(e);
+            if (rc1 && !rc) rc = rc1;
+            if (e->hser_full) {   // (the chunks make this impossible)
+                s.error |= SHD_ERR_HOST_SERIES;
+                if (!rc) rc = SHD_EOVERFLOW;
+            }
+        }
         if (rc == SHD_OK) e->t_done = std::max<uint64_t>(e->t_done, std::min<uint64_t>(stop, g->next));
         s.n_pending_resolved += e->pending_resolved - pend0[k];
     }

@@ -181,6 +181,19 @@ struct shd_eng {
     uint32_t ps_epoch = 1;                  // share tags issued (never 0, never reused)
     double wall_khz = 100000.0;             // device wall clock (wall_clock64) rate
     uint64_t trace_cap = 0;
+    // the host records' series (SHD_QF_HOST_SERIES; DESIGN.md "Host-record series
+    // on the packet engine").  The control block and the sample array are device
+    // memory outside `allocs`: a state copy holds neither.  The array is emptied
+    // into hser_list (append order) often enough that it cannot fill (hser_drain)
+    HserCtl* d_hser = nullptr;
+    shd_host_sample* d_hser_buf = nullptr;
+    uint64_t hser_cap = 0, hser_I = 0;      // samples the array holds; the interval, ns
+    uint64_t hser_q = 1;                    // boundaries per chunk of a run call: max(1, cap / nloc)
+    std::vector<shd_host_sample> hser_list;
+    size_t snap_hser_len = 0;               // hser_list's length when `snap` was taken
+    bool hser_cap_env = false;              // the capacity is SHD_HOST_SERIES_CAP's
+    bool hser_full = false;                 // an append found the array full (SHD_ERR_HOST_SERIES)
+    uint64_t hser_drains = 0, hser_peak = 0, hser_chunks = 0;
 };
 
 // the largest rand_r value x with (double)x / RAND_MAX <= c (-1 if none):
@@ -322,6 +335,20 @@ extern "C" int shd_eng_create(const shd_model* m, shd_pc* pc, int32_t host_begin
     if (host_begin < 0 || host_end > m->n_hosts || host_begin >= host_end) return SHD_EINVAL;
     if (!m->host_vertex || !m->host_rng || !m->bw_down_kibps || !m->bw_up_kibps || !m->dest_cum) return SHD_EINVAL;
     if (m->heartbeat_interval == 0) return SHD_EINVAL;
+    // the host records' series: valid with the records and a nonzero interval
+    // only, boundary indices in 32 bits, and room for a sample per local host
+    uint64_t hser_I = 0, hser_cap = 0;
+    if (m->queue_flags & SHD_QF_HOST_SERIES) {
+        if (!(m->queue_flags & SHD_QF_HOST_RECORDS) || m->hostrec_interval_us == 0) return SHD_EINVAL;
+        hser_I = 1000ull * m->hostrec_interval_us;
+        if (m->end_time / hser_I >= (1ull << 32)) return SHD_EINVAL;
+        const uint64_t nl = (uint64_t)(host_end - host_begin);
+        hser_cap = std::max<uint64_t>(1ull << 18, 2 * nl);
+        if (const char* s = getenv("SHD_HOST_SERIES_CAP")) {   // (tests: a small array, many chunks)
+            hser_cap = strtoull(s, nullptr, 10);
+            if (hser_cap < nl) return SHD_EINVAL;
+        }
+    }
     const int32_t H = m->n_hosts;
     // destination-weight classes: dest_cum is [n_cls][H], host_class picks the row
     const int32_t n_cls = m->n_classes > 1 ? m->n_classes : 1;
@@ -607,7 +634,38 @@ extern "C" int shd_eng_create(const shd_model* m, shd_pc* pc, int32_t host_begin
         int rc;
         if ((rc = ealloc(e, &P.hrec, (size_t)n))) { shd_eng_destroy(e); return rc; }
     }
+    if (hser_I) {
+        // the series: the sample array and its control block, NOT on the
+        // allocation list -- a state copy does not hold them, a restore empties
+        // the array (snapshot_state).  Every record carries its host's index for
+        // the sample's reader (`host` is dead on the device otherwise), and its
+        // pending boundary in _pad (0: none), which travels with the copied state
+        e->hser_I = hser_I;
+        e->hser_cap = hser_cap;
+        e->hser_cap_env = getenv("SHD_HOST_SERIES_CAP") != nullptr;
+        e->hser_q = std::max<uint64_t>(1, hser_cap / (uint64_t)n);
+        HserCtl ctl{};
+        std::vector<shd_tcp_hostrec> init(n);   // (value-initialised: zero)
+        for (size_t i = 0; i < n; i++) init[i].host = (int32_t)(host_begin + (int32_t)i);
+        if (hipMalloc((void**)&e->d_hser_buf, sizeof(shd_host_sample) * hser_cap) != hipSuccess ||
+            hipMalloc((void**)&e->d_hser, sizeof(HserCtl)) != hipSuccess) {
+            shd_eng_destroy(e);
+            return SHD_ENOMEM;
+        }
+        ctl.buf = e->d_hser_buf;
+        ctl.cap = hser_cap;
+        ctl.interval = hser_I;
+        if (hipMemcpyAsync(e->d_hser, &ctl, sizeof(ctl), hipMemcpyHostToDevice, e->stream) != hipSuccess ||
+            hipMemcpyAsync(P.hrec, init.data(), sizeof(shd_tcp_hostrec) * n, hipMemcpyHostToDevice, e->stream) !=
+                hipSuccess ||
+            hipStreamSynchronize(e->stream) != hipSuccess) {
+            shd_eng_destroy(e);
+            return SHD_ENODEV;
+        }
+        P.hser = e->d_hser;
+    }
     P.feat = (m->trace ? F_TRACE : 0u) | (P.hb ? F_HB : 0u) | (P.pcount ? F_PCOUNT : 0u) | (P.hrec ? F_HOSTREC : 0u) |
+             (P.hser ? F_HOSTSER : 0u) |
              (P.host_hb ? F_HOSTHB : 0u) | (P.force_ambig ? F_AMBIG : 0u) |
              ((m->trace && (m->queue_flags & SHD_QF_TRACE_STATUS)) ? F_STATUS : 0u) |
              (P.app != SHD_APP_PHOLD ? F_APP : 0u);
@@ -754,6 +812,43 @@ static int reset_summary(shd_eng* e) {
     DevSummary z = host_fresh_summary();
     SHD_HIP(hipMemcpyAsync(e->d_sum, &z, sizeof(z), hipMemcpyHostToDevice, e->stream));
     SHD_HIP(hipStreamSynchronize(e->stream));
+    return SHD_OK;
+}
+
+// ---- the host records' series: the device's sample array emptied into the
+// host's list.  Called with no round in flight behind it on the stream's
+// order: after every batch and at the end of every run call (the run calls
+// stop at every hser_q-th boundary, so a host appends at most hser_q samples
+// between two of these: no overflow by construction), at the end of every
+// host-driven round, and before every state copy, which is therefore taken
+// with the array empty.  Without the flag: nothing.
+static int hser_drain(shd_eng* e) {
+    if (!e->d_hser) return SHD_OK;
+    HserCtl c{};
+    SHD_HIP(hipMemcpyAsync(&c, e->d_hser, sizeof(c), hipMemcpyDeviceToHost, e->stream));
+    SHD_HIP(hipStreamSynchronize(e->stream));
+    if (c.full) e->hser_full = true;
+    const uint64_t n = std::min<uint64_t>(c.n, e->hser_cap);
+    if (!c.n) return SHD_OK;
+    const size_t at = e->hser_list.size();
+    e->hser_list.resize(at + n);
+    if (n)
+        SHD_HIP(hipMemcpyAsync(e->hser_list.data() + at, e->d_hser_buf, sizeof(shd_host_sample) * n,
+                               hipMemcpyDeviceToHost, e->stream));
+    SHD_HIP(hipMemsetAsync(&e->d_hser->n, 0, sizeof(c.n), e->stream));
+    SHD_HIP(hipStreamSynchronize(e->stream));
+    e->hser_drains++;
+    e->hser_peak = std::max(e->hser_peak, n);
+    return SHD_OK;
+}
+// a restored state copy: the samples appended since it was taken are dropped,
+// on the device and in the list (the rounds that run again append them again)
+static int hser_rewind(shd_eng* e) {
+    if (!e->d_hser) return SHD_OK;
+    SHD_HIP(hipMemsetAsync(&e->d_hser->n, 0, sizeof(unsigned long long), e->stream));
+    SHD_HIP(hipMemsetAsync(&e->d_hser->full, 0, sizeof(uint32_t), e->stream));
+    e->hser_list.resize(std::min(e->hser_list.size(), e->snap_hser_len));
+    e->hser_full = false;
     return SHD_OK;
 }
 
@@ -981,6 +1076,10 @@ extern "C" int shd_eng_end_round(shd_eng* e, shd_round_summary* out) {
     if (!e) return SHD_EINVAL;
     int rc = read_summary(e);
     if (rc) return rc;
+    if (e->d_hser) {   // the round's samples; the caller's windows decide what a round appends
+        if ((rc = hser_drain(e))) return rc;
+        if (e->hser_full) e->h_sum->error |= SHD_ERR_HOST_SERIES;
+    }
     e->parity ^= 1;
     e->round++;
     e->t_done = std::max<uint64_t>(e->t_done, e->round_we);
@@ -1139,6 +1238,14 @@ static void snap_free(shd_eng* e) {
     e->snap_kind.clear();
 }
 static int snapshot_state(shd_eng* e, bool restore) {
+    // the series: a copy is taken with the sample array empty and remembers the
+    // list's length; a restore goes back to both (the pending boundaries are in
+    // the records, which are copied state)
+    if (e->d_hser) {
+        const int rc = restore ? hser_rewind(e) : hser_drain(e);
+        if (rc) return rc;
+        if (!restore) e->snap_hser_len = e->hser_list.size();
+    }
     if (!restore && e->snap.size() != e->allocs.size()) {
         bool warned = false;
         for (size_t i = e->snap.size(); i < e->allocs.size(); i++) {
@@ -1310,6 +1417,7 @@ extern "C" int shd_eng_round_retry(shd_eng* e, const shd_pending* all, uint64_t 
 // copy are restored with it and assigned again in the same serial order), so
 // a send is undecided in the replay only if it was undecided and decidable
 // the first time.  No snapshot of the round itself is needed.
+static int run_until_one(shd_eng* e, uint64_t t_stop, shd_run_stats* st);
 static int replay_ambiguous(shd_eng* e, uint64_t ws, uint64_t stop, shd_round_summary* r, shd_run_stats* s) {
     if (!e->snap_valid || e->in_replay) return SHD_EAMBIG;
     int rc = snapshot_state(e, true);
@@ -1343,7 +1451,7 @@ static int replay_ambiguous(shd_eng* e, uint64_t ws, uint64_t stop, shd_round_su
     for (const uint64_t b : stops) {
         if (b <= e->h_sum->next_time || b > ws) continue;
         shd_run_stats sub{};
-        rc = shd_eng_run_until(e, b, &sub);
+        rc = run_until_one(e, b, &sub);
         sub_ms += sub.device_ms_round_kernel;
         s->n_rounds_rerun += sub.n_rounds_rerun;
         if (rc) break;
@@ -1360,7 +1468,7 @@ static int replay_ambiguous(shd_eng* e, uint64_t ws, uint64_t stop, shd_round_su
     return rc;
 }
 
-extern "C" int shd_eng_run_until(shd_eng* e, uint64_t t_stop, shd_run_stats* st) {
+static int run_until_one(shd_eng* e, uint64_t t_stop, shd_run_stats* st) {
     if (!e) return SHD_EINVAL;
     // a partial engine's sends to hosts outside it leave by rounds
     // (shd_eng_run_round + shd_eng_take_remote) or a group, never a batch
@@ -1463,6 +1571,7 @@ extern "C" int shd_eng_run_until(shd_eng* e, uint64_t t_stop, shd_run_stats* st)
             float ms = 0;
             if (hipEventElapsedTime(&ms, e->bev[0], e->bev[1]) == hipSuccess) s.device_ms_launches += ms;
         }
+        if ((rc = hser_drain(e))) break;   // (the series: the batch's samples)
         // ticketless batches unless first touches come thick: a ticketless
         // round that logs halts its batch for the host's resolution, a
         // ticketed one resolves a small log on the device.  After a batch
@@ -1563,6 +1672,14 @@ extern "C" int shd_eng_run_until(shd_eng* e, uint64_t t_stop, shd_run_stats* st)
         }
     }
     e->h_sum->next_time = next;
+    if (e->d_hser) {   // the series: the array is empty between run calls (shd_eng_host_series reads the list)
+        const int rc1 = hser_drain(e);
+        if (rc1 && !rc) rc = rc1;
+        if (e->hser_full) {   // (the chunks make this impossible: shd_eng_run_until)
+            s.error |= SHD_ERR_HOST_SERIES;
+            if (!rc) rc = SHD_EOVERFLOW;
+        }
+    }
     // every event before `stop` has run: the engine's clock stands at stop
     if (rc == SHD_OK) e->t_done = std::max<uint64_t>(e->t_done, std::min<uint64_t>(stop, next));
     if (rc == SHD_OK && e->snap_valid && !e->in_replay && stop > e->snap_next &&
@@ -1623,6 +1740,51 @@ extern "C" int shd_debug_prof(uint64_t* out, int n) {
     return SHD_OK;
 }
 #endif
+
+// the series' chunks: the q-th boundary after `from`, or `stop`
+static uint64_t hser_chunk_stop(const shd_eng* e, uint64_t from, uint64_t stop, uint64_t q) {
+    const uint64_t k = from / e->hser_I + q;
+    return k > stop / e->hser_I ? stop : std::min<uint64_t>(k * e->hser_I, stop);
+}
+static void add_stats(shd_run_stats& a, const shd_run_stats& b) {
+    a.n_rounds += b.n_rounds; a.n_events += b.n_events; a.n_pkt_events += b.n_pkt_events;
+    a.n_pending_resolved += b.n_pending_resolved;
+    a.window_ns = b.window_ns;
+    if (b.final_time) a.final_time = b.final_time;
+    a.device_ms_round_kernel += b.device_ms_round_kernel; a.wall_ms += b.wall_ms;
+    a.device_ms_launches += b.device_ms_launches;
+    a.error |= b.error;
+    a.n_batches_ticketless += b.n_batches_ticketless; a.n_rounds_protected += b.n_rounds_protected;
+    a.n_rounds_rerun += b.n_rounds_rerun; a.n_host_rounds += b.n_host_rounds; a.n_batches += b.n_batches;
+    a.n_batches_persistent += b.n_batches_persistent; a.n_batches_sparse += b.n_batches_sparse;
+    a.n_rounds_replayed += b.n_rounds_replayed; a.n_restore_points += b.n_restore_points;
+    a.n_batches_fused += b.n_batches_fused;
+}
+
+// With the host records' series a run call advances in chunks that end at the
+// hser_q-th boundary after the chunk's start (run_until_one stops there as at
+// any t_stop, recorded in snap_stops like any other, and empties the sample
+// array): within a chunk a host's touches lie in at most hser_q intervals, so
+// it appends at most hser_q samples and hser_q x nloc fit the array.  Results
+// do not depend on where a run stops.  Without the flag: one call, unchanged.
+extern "C" int shd_eng_run_until(shd_eng* e, uint64_t t_stop, shd_run_stats* st) {
+    if (!e) return SHD_EINVAL;
+    if (!e->d_hser) return run_until_one(e, t_stop, st);
+    const uint64_t stop = std::min<uint64_t>(t_stop, e->P.end_time);
+    shd_run_stats tot{};
+    uint64_t from = e->t_done;
+    int rc;
+    do {
+        const uint64_t cs = hser_chunk_stop(e, from, stop, e->hser_q);
+        if (cs < stop) e->hser_chunks++;
+        shd_run_stats s{};
+        rc = run_until_one(e, cs, &s);
+        add_stats(tot, s);
+        from = std::max(from, cs);
+    } while (rc == SHD_OK && from < stop);
+    if (st) *st = tot;
+    return rc;
+}
 
 extern "C" int shd_eng_run(shd_eng* e, shd_run_stats* st) {
     if (!e) return SHD_EINVAL;
@@ -1723,6 +1885,19 @@ extern "C" int shd_eng_heartbeats(shd_eng* e, uint32_t* out, uint64_t cap, uint6
     return SHD_OK;
 }
 
+// what the device does not keep of a record: what the queue holds, and the byte
+// counts -- every datagram of the model carries `payload` bytes (the [STATUS]
+// line's bytes=); _pad is the series' pending boundary on the device
+static void hrec_fill(shd_tcp_hostrec& r, uint64_t payload) {
+    r._pad = 0;
+    r.depth_end = (uint32_t)(r.router_enqueued - r.router_dequeued - r.router_dropped);
+    r.router_enqueued_bytes = r.router_enqueued * payload;
+    r.router_dequeued_bytes = r.router_dequeued * payload;
+    r.router_dropped_bytes = r.router_dropped * payload;
+    r.if_received_bytes = r.if_received * payload;
+    r.if_sent_bytes = r.if_sent * payload;
+}
+
 extern "C" int shd_eng_host_records(shd_eng* e, shd_tcp_hostrec* out, uint64_t cap, uint64_t* n) {
     if (!e || !n || (cap && !out)) return SHD_EINVAL;
     if (!e->P.hrec) return SHD_EINVAL;   // SHD_QF_HOST_RECORDS was not set
@@ -1733,20 +1908,59 @@ extern "C" int shd_eng_host_records(shd_eng* e, shd_tcp_hostrec* out, uint64_t c
     SHD_HIP(hipSetDevice(e->device));
     SHD_HIP(hipMemcpyAsync(out, e->P.hrec, sizeof(shd_tcp_hostrec) * cnt, hipMemcpyDeviceToHost, e->stream));
     SHD_HIP(hipStreamSynchronize(e->stream));
-    // what the device does not keep: the host index, what the queue still
-    // holds, and the byte counts -- every datagram of the model carries
-    // `payload` bytes (the [STATUS] line's bytes=)
-    const uint64_t payload = e->P.payload;
     for (uint64_t i = 0; i < cnt; i++) {
-        shd_tcp_hostrec& r = out[i];
-        r.host = (int32_t)(e->P.h0 + (int32_t)i);
-        r.depth_end = (uint32_t)(r.router_enqueued - r.router_dequeued - r.router_dropped);
-        r.router_enqueued_bytes = r.router_enqueued * payload;
-        r.router_dequeued_bytes = r.router_dequeued * payload;
-        r.router_dropped_bytes = r.router_dropped * payload;
-        r.if_received_bytes = r.if_received * payload;
-        r.if_sent_bytes = r.if_sent * payload;
+        out[i].host = (int32_t)(e->P.h0 + (int32_t)i);   // the model's host index
+        hrec_fill(out[i], e->P.payload);
     }
+    return SHD_OK;
+}
+
+// The series' samples up to the horizon (t_done: the stop of the last run call
+// or the window end of the last host-driven round): the list (every appended
+// sample has T <= the time of the count that appended it, which has run), and
+// for every host whose pending boundary is <= the horizon and < end_time the
+// record as it stands -- every event before that boundary has run, and only a
+// count at or past it changes the record.  Nothing on the device changes: a
+// later append of that sample lands in the list and replaces the synthesised
+// one.
+extern "C" int shd_eng_host_series(shd_eng* e, shd_host_sample* out, uint64_t cap, uint64_t* n) {
+    if (!e || !n || (cap && !out)) return SHD_EINVAL;
+    if (!e->d_hser) return SHD_EINVAL;   // SHD_QF_HOST_SERIES was not set
+    const uint64_t nloc = (uint64_t)e->nloc, I = e->hser_I, horizon = e->t_done;
+    SHD_HIP(hipSetDevice(e->device));
+    std::vector<shd_tcp_hostrec> recs(nloc);
+    SHD_HIP(hipMemcpyAsync(recs.data(), e->P.hrec, sizeof(shd_tcp_hostrec) * nloc, hipMemcpyDeviceToHost, e->stream));
+    SHD_HIP(hipStreamSynchronize(e->stream));
+    uint64_t cnt = e->hser_list.size();
+    for (const shd_tcp_hostrec& r : recs) {
+        const uint64_t T = (uint64_t)r._pad * I;
+        if (r._pad && T <= horizon && T < e->P.end_time) cnt++;
+    }
+    *n = cnt;
+    if (cap < cnt) return SHD_ERANGE;
+    uint64_t at = 0;
+    for (const shd_host_sample& s : e->hser_list) out[at++] = s;
+    for (const shd_tcp_hostrec& r : recs) {
+        const uint64_t T = (uint64_t)r._pad * I;
+        if (r._pad && T <= horizon && T < e->P.end_time) {
+            out[at].t = T;
+            out[at++].rec = r;
+        }
+    }
+    for (uint64_t i = 0; i < cnt; i++) hrec_fill(out[i].rec, e->P.payload);   // (rec.host: set at creation)
+    std::sort(out, out + cnt, [](const shd_host_sample& a, const shd_host_sample& b) {
+        return a.rec.host != b.rec.host ? a.rec.host < b.rec.host : a.t < b.t;
+    });
+    return SHD_OK;
+}
+
+extern "C" int shd_eng_host_series_info(shd_eng* e, uint64_t out[5]) {
+    if (!e || !out || !e->d_hser) return SHD_EINVAL;
+    out[0] = e->hser_list.size();
+    out[1] = e->hser_drains;
+    out[2] = e->hser_peak;
+    out[3] = e->hser_cap;
+    out[4] = e->hser_chunks;
     return SHD_OK;
 }
 
@@ -1796,6 +2010,8 @@ extern "C" void shd_eng_destroy(shd_eng* e) {
     (void)hipSetDevice(e->device);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     for (void* p : e->allocs) (void)hipFree(p);
+    if (e->d_hser) (void)hipFree(e->d_hser);
+    if (e->d_hser_buf) (void)hipFree(e->d_hser_buf);
     snap_free(e);   // the protected rounds' / restore point's state copy
     if (e->h_sum) (void)hipHostFree(e->h_sum);
     if (e->h_ring) (void)hipHostFree(e->h_ring);

@@ -26,6 +26,8 @@ SHD_QF_HEARTBEATS = 4       # queue_flags: tracker node counters at every heartb
 SHD_QF_NO_APP_START = 8     # queue_flags: the caller pushes the application starts (shd_eng_push_events)
 SHD_QF_TRACE_STATUS = 16    # queue_flags: with trace, the application's records too (status_lines)
 SHD_QF_HOST_RECORDS = 32    # queue_flags: one TcpHostRec per host from the packet engine (Engine.host_records)
+SHD_QF_HOST_SERIES = 64     # queue_flags: with HOST_RECORDS, a sample of the record per touched interval (Engine.host_series)
+ERR_HOST_SERIES = 256       # shd_round_summary.error: the series' sample array filled (SHD_ERR_HOST_SERIES)
 ERR_AMBIGUOUS = 16          # shd_round_summary.error: an ambiguous first-touch drop decision (SHD_ERR_AMBIGUOUS)
 SHD_PHOLD_LISTEN_PORT = 8998   # PHOLD_LISTEN_PORT, test_phold.c:34
 SHD_MIN_RANDOM_PORT = 10000    # MIN_RANDOM_PORT, definitions.h:94
@@ -126,7 +128,8 @@ class Model(C.Structure):
         ("host_class", P(C.c_uint8)), ("n_classes", C.c_int32), ("_pad1", C.c_int32),
         ("host_heartbeat", P(C.c_uint64)),
         ("app", C.c_uint32), ("_pad2", C.c_int32), ("app_peer", P(C.c_int32)),
-        ("app_spec", P(UdpApp)), ("host_app", P(C.c_uint8)), ("n_app_specs", C.c_uint32), ("_pad3", C.c_uint32),
+        ("app_spec", P(UdpApp)), ("host_app", P(C.c_uint8)), ("n_app_specs", C.c_uint32),
+        ("hostrec_interval_us", C.c_uint32),
     ]
 
 
@@ -426,6 +429,8 @@ _SIGS = {
     "shd_eng_path_counts": (C.c_int, [C.c_void_p, P(C.c_uint64), C.c_uint64, P(C.c_uint64)]),
     "shd_eng_heartbeats": (C.c_int, [C.c_void_p, P(C.c_uint32), C.c_uint64, P(C.c_uint64)]),
     "shd_eng_host_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, P(C.c_uint64)]),
+    "shd_eng_host_series": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, P(C.c_uint64)]),
+    "shd_eng_host_series_info": (C.c_int, [C.c_void_p, P(C.c_uint64)]),
     "shd_eng_stream": (C.c_int, [C.c_void_p, P(C.c_void_p)]),
     "shd_status_lines": (C.c_int, [C.c_void_p, C.c_uint64, P(C.c_uint32), P(C.c_uint32), C.c_uint32, C.c_uint32,
                                    C.c_uint32, P(C.c_int32), P(P(Lines))]),
@@ -704,6 +709,56 @@ def merge_tcp_hosts(parts) -> np.ndarray:
     return out
 
 
+# one sample of a host-record series (struct shd_host_sample, include/shdtcp.h): the boundary and the record
+HOST_SAMPLE_DTYPE = np.dtype([("t", "<u8"), ("rec", TCP_HOSTREC_DTYPE)])
+HOST_SERIES_CSV_FIELDS = ("t",) + HOSTS_CSV_FIELDS
+
+
+def write_host_series_csv(path, samples) -> int:
+    """Write host-record samples (HOST_SAMPLE_DTYPE, as sim.Engine.host_series()
+    returns them) as CSV: a header line (HOST_SERIES_CSV_FIELDS: t, then
+    write_hosts_csv's columns), then one line per sample in the samples'
+    order; times in ns.  Returns the number of rows."""
+    a = np.asarray(samples, dtype=HOST_SAMPLE_DTYPE)
+    scalars = HOSTS_CSV_FIELDS[:-HOSTS_HIST_BUCKETS]
+    with open(path, "w") as out:
+        out.write(",".join(HOST_SERIES_CSV_FIELDS) + "\n")
+        for s in a:
+            r = s["rec"]
+            out.write(",".join([str(int(s["t"]))] + [str(int(r[k])) for k in scalars] +
+                               [str(int(v)) for v in r["sojourn_hist"]]) + "\n")
+    return len(a)
+
+
+def merge_host_series(parts) -> np.ndarray:
+    """The host-record samples of a group's ranks (HOST_SAMPLE_DTYPE arrays, each
+    rank its own hosts') as the one-engine array: concatenated and sorted by
+    (host, t)."""
+    parts = [np.asarray(a, dtype=HOST_SAMPLE_DTYPE) for a in parts]
+    out = np.concatenate(parts) if parts else np.zeros(0, dtype=HOST_SAMPLE_DTYPE)
+    return out[np.lexsort((out["t"], out["rec"]["host"]))]
+
+
+def host_progress(samples, host, interval_ns, end_ns) -> np.ndarray:
+    """One host's series as a dense HOST_SAMPLE_DTYPE array with a row per
+    boundary T_k = k * interval_ns < end_ns, k >= 1: the host's sparse samples
+    filled forward (a boundary without a sample repeats the record of the last
+    one before it), zero apart from `t` and `host` before its first sample."""
+    a = np.asarray(samples, dtype=HOST_SAMPLE_DTYPE)
+    a = a[a["rec"]["host"] == int(host)]
+    a = a[np.argsort(a["t"], kind="stable")]
+    interval_ns, end_ns = int(interval_ns), int(end_ns)
+    K = max((end_ns - 1) // interval_ns, 0)   # boundaries k * I < end, k >= 1
+    out = np.zeros(K, dtype=HOST_SAMPLE_DTYPE)
+    out["t"] = (np.arange(K, dtype=np.uint64) + np.uint64(1)) * np.uint64(interval_ns)
+    out["rec"]["host"] = int(host)
+    if len(a) and K:
+        assert ((a["t"] % np.uint64(interval_ns)) == 0).all() and a["t"].min() > 0 and a["t"].max() <= out["t"][-1]
+        at = np.searchsorted(a["t"], out["t"], side="right") - 1   # the last sample at or before each boundary
+        out["rec"][at >= 0] = a["rec"][at[at >= 0]]
+    return out
+
+
 def tcp_result_series(res):
     """The samples of a shd_tcp_result (pointer) as a TCP_SAMPLE_DTYPE array of
     its own, sorted by (flow, t) (shd_tcp_result_series), and the drains'
@@ -799,14 +854,15 @@ class ModelArrays:
                  app_start=1 * SHD_SEC, load=16, payload=1, heartbeat_interval=SHD_SEC,
                  bootstrap_end=0, trace=False, evq_cap=0, inbox_cap=0, codelq_cap=0,
                  txq_cap=0, queue_flags=0, host_class=None, host_heartbeat=None, app_peer=None,
-                 app_specs=None, host_app=None):
+                 app_specs=None, host_app=None, hostrec_interval_us=0):
         """dest_cum: [H] (one weights row for every host) or [n_classes, H] with
         host_class [H] picking each host's row; host_heartbeat: [H] ns or None;
         app_peer: None (every host runs PHOLD) or [H] -1 | server host (every
         host runs the UDP request/response echo, SHD_APP_UDP_ECHO);
         app_specs: [(send, dest, n_start, per_read)] with host_app [H] picking
         each host's (SHD_APP_UDP, include/shdgpu.h shd_udp_app; app_peer then
-        names the SHD_DEST_PEER hosts' peers)."""
+        names the SHD_DEST_PEER hosts' peers); hostrec_interval_us: the
+        sampling interval of SHD_QF_HOST_SERIES (ignored without the flag)."""
         self.host_vertex = np.ascontiguousarray(host_vertex, dtype=np.int32)
         self.host_rng = np.ascontiguousarray(host_rng, dtype=np.uint32)
         self.bw_down = np.ascontiguousarray(bw_down, dtype=np.uint64)
@@ -839,7 +895,7 @@ class ModelArrays:
         self.params = dict(end_time=int(end_time), app_start=int(app_start), load=int(load),
                            payload=int(payload), heartbeat_interval=int(heartbeat_interval),
                            bootstrap_end=int(bootstrap_end), trace=int(bool(trace)),
-                           queue_flags=int(queue_flags))
+                           queue_flags=int(queue_flags), hostrec_interval_us=int(hostrec_interval_us))
         self.struct = Model(
             H, 0, as_ptr(self.host_vertex, C.c_int32), as_ptr(self.host_rng, C.c_uint32),
             as_ptr(self.bw_down, C.c_uint64), as_ptr(self.bw_up, C.c_uint64),
@@ -851,7 +907,7 @@ class ModelArrays:
             self.app, 0, None if self.app_peer is None else as_ptr(self.app_peer, C.c_int32),
             None if self.app_specs is None else C.cast(self.app_specs, P(UdpApp)),
             None if self.host_app is None else as_ptr(self.host_app, C.c_uint8),
-            0 if self.app_specs is None else len(self.app_specs), 0)
+            0 if self.app_specs is None else len(self.app_specs), int(hostrec_interval_us))
 
     @property
     def n_hosts(self):

@@ -245,6 +245,30 @@ class Engine:
                                              C.byref(n)), "shd_eng_host_records")
         return out[:n.value]
 
+    def host_series(self) -> np.ndarray:
+        """The host records' per-interval samples so far (SHD_QF_HOST_SERIES with
+        a hostrec_interval_us; shd_eng_host_series) as an S.HOST_SAMPLE_DTYPE
+        array sorted by (host, t): for every interval in which a local host's
+        record was touched, the record as it stood at the interval's end.  The
+        call reads and resets nothing; S.write_host_series_csv writes the
+        array, S.merge_host_series joins a group's ranks and S.host_progress
+        fills one host's samples forward."""
+        n = C.c_uint64()
+        rc = S.lib().shd_eng_host_series(self.ptr, None, 0, C.byref(n))
+        if rc != -34:   # SHD_ERANGE with the count, unless there is nothing (or an error)
+            S.check(rc, "shd_eng_host_series")
+            return np.zeros(0, dtype=S.HOST_SAMPLE_DTYPE)
+        out = np.zeros(n.value, dtype=S.HOST_SAMPLE_DTYPE)
+        S.check(S.lib().shd_eng_host_series(self.ptr, out.ctypes.data, len(out), C.byref(n)), "shd_eng_host_series")
+        return out[:n.value]
+
+    def host_series_info(self) -> dict:
+        """dict(samples, drains, peak, capacity, chunks): what the series took off
+        the device so far (shd_eng_host_series_info)"""
+        v = (C.c_uint64 * 5)()
+        S.check(S.lib().shd_eng_host_series_info(self.ptr, v), "shd_eng_host_series_info")
+        return dict(zip(("samples", "drains", "peak", "capacity", "chunks"), map(int, v)))
+
     def status_lines(self, ips, host_ids=None, listen_port=S.SHD_PHOLD_LISTEN_PORT) -> list:
         """[(time_ns, host, line)]: the [STATUS] lines of the engine's trace, made
         by the library (shd_eng_status_lines, packet.c:647-659)"""

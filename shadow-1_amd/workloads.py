@@ -201,13 +201,19 @@ def phold_cum(weights) -> np.ndarray:
 
 def phold_model(host_vertex, *, end_time, seed=1, bw_down=10240, bw_up=10240, load=16,
                 payload=1, app_start=S.SHD_SEC, heartbeat=S.SHD_SEC, bootstrap_end=0,
-                trace=False, dest_cum=None, host_class=None, host_rng=None, hosts=False, **caps) -> S.ModelArrays:
+                trace=False, dest_cum=None, host_class=None, host_rng=None, hosts=False, host_series_us=0,
+                **caps) -> S.ModelArrays:
     """PHOLD-UDP hosts; dest_cum None = uniform weights over all hosts, else
     [H] or [n_classes, H] (then host_class [H]); host_rng None = the seed
     chain after the attach draw (one random pick per host); hosts: keep a host
-    record per host (SHD_QF_HOST_RECORDS, sim.Engine.host_records)."""
+    record per host (SHD_QF_HOST_RECORDS, sim.Engine.host_records);
+    host_series_us (with hosts): also a sample of it per touched interval of
+    that many us (SHD_QF_HOST_SERIES, sim.Engine.host_series)."""
     H = len(host_vertex)
     caps["queue_flags"] = caps.get("queue_flags", 0) | (S.SHD_QF_HOST_RECORDS if hosts else 0)
+    if host_series_us:
+        caps["queue_flags"] |= S.SHD_QF_HOST_SERIES
+        caps["hostrec_interval_us"] = int(host_series_us)
     seeds = after_attach_draw(seed_chain(H, seed)) if host_rng is None else host_rng
     bd = np.broadcast_to(np.asarray(bw_down, dtype=np.uint64), (H,)).copy()
     bu = np.broadcast_to(np.asarray(bw_up, dtype=np.uint64), (H,)).copy()
