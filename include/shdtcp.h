@@ -50,7 +50,11 @@
  * out of order -- counted by the host's own lane where the reference raises
  * the status, TCP packets and the datagrams of a mixed model alike, and copied
  * to the host at the end (shd_tcp_result_hosts; tests/test_tcp_hosts_gpu.py
- * against tests/golden/ref_tcp_hosts.json).
+ * against tests/golden/ref_tcp_hosts.json).  With SHD_TCP_OPT_HOST_SERIES
+ * beside it, a sample of each host's record for every interval in which it
+ * changed says when the queue built up (shd_host_sample,
+ * shd_tcp_model.host_series_interval_us, shd_tcp_result_host_series;
+ * tests/test_tcp_hseries_gpu.py against tests/golden/ref_tcp_hseries.json).
  *
  * A host's shape comes from the model.  Its socket slots are the sockets it
  * can ever create -- a socket is not released in a TCP run: for each of its
@@ -92,6 +96,8 @@ typedef struct shd_tcp_model {
     const uint64_t* bw_down_kibps;    /* [H]                                            */
     const uint64_t* bw_up_kibps;      /* [H]                                            */
     int32_t n_vertices;               /* V: the attached vertices the tables index      */
+    int32_t host_series_cap;          /* SHD_TCP_OPT_HOST_SERIES: records of the sample array
+                                         (host_series_interval_us, below)                */
     const int32_t* host_vertex;       /* [H] each host's vertex index in [0, V)         */
     const double* path_lat_ms;        /* [V*V] src_vertex*V + dst_vertex; < 0: no route
                                          (pairs no host pair uses may be left < 0)       */
@@ -109,6 +115,39 @@ typedef struct shd_tcp_model {
     uint32_t qdisc;                   /* --interface-qdisc (options.c:162): 0 fifo, 1 rr
                                          (network_interface.c:466-517)                    */
     uint32_t options;                 /* SHD_TCP_OPT_* bits; the others are reserved and ignored */
+    /* SHD_TCP_OPT_HOST_SERIES: the sampling interval I of the host records'
+     * series in microseconds (I = 1000 * host_series_interval_us ns; nonzero
+     * with the option, ignored without), by the packet engine's rule
+     * (shdgpu.h SHD_QF_HOST_SERIES).  The boundaries are T_k = k * I, k >= 1,
+     * T_k < end_time; a model with end_time / I >= 2^32 is refused (-22).  A
+     * host's record is touched by each of the eight statuses it counts
+     * (shd_tcp_hostrec).  A touch at t yields one shd_host_sample labelled
+     * with the first boundary after it, (t / I + 1) * I -- a status raised at
+     * exactly T_k belongs to the interval after it -- holding the host's whole
+     * record after every one of its events before that boundary, depth_end
+     * the queue's length then.  An interval without a touch yields no sample,
+     * and neither does a boundary that is not before end_time.  The host's
+     * own lane appends the samples to one engine-wide array in device memory,
+     * emptied into host memory where the flow series' array is (shd_tcp_run:
+     * after every batch of 64 rounds; a group: after 64 rounds at the latest,
+     * or once the array is past half), so a series is as long as the run.
+     * host_series_cap: records of that array, 240 bytes each (<= 0: the
+     * default, the larger of 2^18 and sixteen per host of the engine; at most
+     * 2^24, more is refused with -22).  Sizing rule: between two drains a
+     * host appends at most one sample per boundary it crosses with a touch:
+     * a round's touches lie within one window W (the smallest path latency),
+     * so no more than 64 * (W / I + 1) per host of the engine, and seldom
+     * more than one at an interval above W.  An append that finds the array
+     * full writes nothing and sets
+     * SHD_TCP_ERR_HSERIES.  (The field sits in what was padding after
+     * `options`, and host_series_cap in the padding after n_vertices: the
+     * struct keeps its size and every other field its offset, so a caller
+     * built against the older header passes the same bytes; both are read
+     * only with the option's bit.  Such a caller's uninitialised padding is
+     * harmless only because bit 16 of `options` was reserved and ignored: a
+     * caller that set that bit by accident is now refused with -22 or runs
+     * with the series.) */
+    uint32_t host_series_interval_us;
     /* A built path cache of this model's graph (shdgpu.h shd_pc_create: an
      * undirected graph, the hosts' vertices attached), or NULL.  Set: every
      * path query of the run goes to the cache's device tables under the lazy
@@ -453,7 +492,8 @@ typedef struct shd_tcp_hostrec {
 } shd_tcp_hostrec;
 
 /* One sample of a host-record series (the packet engine's SHD_QF_HOST_SERIES,
- * shdgpu.h shd_eng_host_series): `rec` is host rec.host's whole record as it
+ * shdgpu.h shd_eng_host_series, and the TCP path's SHD_TCP_OPT_HOST_SERIES,
+ * shd_tcp_result_host_series): `rec` is host rec.host's whole record as it
  * stood after every event of the host before the boundary `t` (ns, a multiple
  * of the interval), depth_end the queue's length at `t`.  A host has a sample
  * for boundary t only if one of the record's statuses was raised on it in the
@@ -466,9 +506,11 @@ typedef struct shd_host_sample {
 } shd_host_sample;   /* 240 B */
 
 /* shd_tcp_model.options: independent bits, but SHD_TCP_OPT_SERIES is valid only
- * together with SHD_TCP_OPT_FLOWS and a nonzero series_interval_us (-22
- * otherwise, before any device call) */
-enum { SHD_TCP_OPT_FLOWS = 1, SHD_TCP_OPT_PATHS = 2, SHD_TCP_OPT_SERIES = 4, SHD_TCP_OPT_HOSTS = 8 };
+ * together with SHD_TCP_OPT_FLOWS and a nonzero series_interval_us, and
+ * SHD_TCP_OPT_HOST_SERIES only together with SHD_TCP_OPT_HOSTS and a nonzero
+ * host_series_interval_us (-22 otherwise, before any device call) */
+enum { SHD_TCP_OPT_FLOWS = 1, SHD_TCP_OPT_PATHS = 2, SHD_TCP_OPT_SERIES = 4, SHD_TCP_OPT_HOSTS = 8,
+       SHD_TCP_OPT_HOST_SERIES = 16 };
 
 /* The most entries the device's pair table gets (SHD_TCP_OPT_PATHS; 64 bytes
  * each: 256 MiB).  Its capacity is a power of two at least twice min(Vu^2, E +
@@ -499,8 +541,11 @@ enum {
     SHD_TCP_ERR_PCAP = 1024,  /* a capture ring filled between two drains (pcap_ring) */
     SHD_TCP_ERR_PATHS = 2048, /* the device's pair table had no free entry for a vertex pair (SHD_TCP_OPT_PATHS):
                                  counts could not be placed, the path records are incomplete */
-    SHD_TCP_ERR_SERIES = 4096 /* the sample array filled between two drains (SHD_TCP_OPT_SERIES, series_cap):
+    SHD_TCP_ERR_SERIES = 4096, /* the sample array filled between two drains (SHD_TCP_OPT_SERIES, series_cap):
                                  the sample was not written, the series is incomplete */
+    SHD_TCP_ERR_HSERIES = 8192 /* the host records' sample array filled between two drains
+                                  (SHD_TCP_OPT_HOST_SERIES, host_series_cap): the sample was not written, and
+                                  the series holds the samples appended before it only */
 };
 
 /* Run the model to end_time on the current HIP device (the reference's
@@ -576,6 +621,22 @@ int shd_tcp_result_series(const shd_tcp_result* r, const shd_tcp_sample** recs, 
  * run with the option print, on stderr, the size and the host wall time of
  * the records' copy at its end (measurements: profiles/hosts/ab.txt). */
 int shd_tcp_result_hosts(const shd_tcp_result* r, const shd_tcp_hostrec** recs, uint64_t* n);
+
+/* The host records' series of the hosts this result covers (a result of
+ * shd_tcp_run / shd_tcp_run_group only), sorted by (rec.host, t), rec.host the
+ * model's host index and rec._pad 0: a group's rank returns its own hosts'
+ * samples -- nothing is exchanged -- and the ranks' arrays joined and sorted
+ * are the one-engine array.  A host whose last touched interval ends before
+ * end_time has its final record as that boundary's sample.  info, when not
+ * NULL, takes the drains' figures.  *recs NULL and *n 0 (info zero) when the
+ * model did not set SHD_TCP_OPT_HOST_SERIES.  Owned by the result.  Returns 0,
+ * -22 for a NULL r, recs or n.  Without the option a run allocates nothing
+ * for the series and launches nothing extra; a rerun from the start
+ * (first_touch_reruns) starts the series again with the records.
+ * SHD_TCP_SERIES_TIMING in the environment (any value) makes a run with the
+ * option print, on stderr, the samples, the drains and their host wall time. */
+int shd_tcp_result_host_series(const shd_tcp_result* r, const shd_host_sample** recs, uint64_t* n,
+                               shd_tcp_series_info* info);
 
 /* The same model on a group of engines, one per process and GPU (shdgpu.h
  * shd_comm: RCCL, or the host-memory transport for several processes on one

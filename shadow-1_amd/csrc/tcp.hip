@@ -44,7 +44,12 @@
 // (series_drain), and what is still touched at the end by k_tcp_series_flush.
 // With SHD_TCP_OPT_HOSTS each host's lane counts what its router queue, its
 // interface and its sockets' throttled and unordered queues did into the
-// host's shd_tcp_hostrec (host_status), copied to the host at the end.
+// host's shd_tcp_hostrec (host_status), copied to the host at the end; with
+// SHD_TCP_OPT_HOST_SERIES a host's lane appends the record as it stands where
+// it crosses an interval boundary that the record was touched before
+// (series_cross, host_sample) to one engine-wide sample array, emptied between
+// batches of rounds like the flow series', and k_tcp_hseries_flush takes what
+// is still touched at the end.
 //
 // The work is branchy per-host control flow with a few events per host and
 // round: latency-bound by design ("TCP"); it shares nothing with
@@ -464,7 +469,8 @@ struct Glob {
     uint32_t* pt_full;
     uint32_t pt_mask, path_on;
     // flow time series (SHD_TCP_OPT_SERIES, with flow records only): ser_on is
-    // the one launch-uniform word the round's event loop tests; the engine-wide
+    // the one launch-uniform word the round's event loop tests (bit 0: this
+    // series, bit 1: the host records' series below); the engine-wide
     // sample array ser [ser_cap] and its append counter *nser (emptied between
     // batches of rounds: series_drain), each local host's next boundary
     // ser_next [nloc] and the interval in ns.  All null / 0 without the option.
@@ -477,6 +483,16 @@ struct Glob {
     // its public form, written by the host's own lane only with plain stores;
     // null without the option.  stat_on's fourth bit (8) says they are kept.
     shd_tcp_hostrec* hrec;
+    // their per-interval series (SHD_TCP_OPT_HOST_SERIES, with host records
+    // only; ser_on's bit 1): the engine-wide sample array hser [hser_cap] and
+    // its append counter *nhser (emptied where the flow series' array is), each
+    // local host's next boundary hser_next [nloc] and the interval in ns.  All
+    // null / 0 without the option.
+    shd_host_sample* hser;
+    uint32_t* nhser;
+    uint64_t* hser_next;
+    uint64_t hser_ival;
+    uint32_t hser_cap;
 };
 struct XSegHead { uint32_t n, nsack, err, _pad[13]; };   // 64 B, then xcap Mails, then xsack_cap SACK words
 static_assert(sizeof(XSegHead) == 64, "segment header");
@@ -3339,22 +3355,74 @@ __device__ uint32_t series_take(const Glob& g, int32_t h, uint64_t t) {
     }
     return err;
 }
-// how far host h's lane runs before it has to look at its boundary: the
-// window's end, or the boundary when that comes first
-__device__ __noinline__ uint64_t series_limit(const Glob& g, int32_t h, uint64_t wend) {
-    const uint64_t nb = g.ser_next[h];
-    return nb < wend ? nb : wend;
+// Host h's record sampled at boundary t (the host records' series), if one of
+// its statuses was raised in the interval that ends there: the lane stands
+// before its first event at or past t, so the record is the one after every
+// event of the host before t -- only counts change it -- and t_last says
+// whether the interval [t - I, t) touched it (no event of the host lies
+// between the boundary before t and the event that set this one).  One record
+// appended to the engine's array, its place taken with an atomic add (hosts
+// sit in different waves and blocks), written with plain stores.  depth_end is
+// the sampled counts' enqueued - dequeued - dropped, never DHost::cq_n:
+// K_DELIVER puts the entry into the ring before it raises ROUTER_ENQUEUED.
+// An append past the capacity writes nothing and returns the error bit.
+// t_first == 0 reads as "never touched", host_status's own convention: a
+// status raised at time 0 alone would yield no sample for the first boundary
+// (no process starts at 0, and a packet takes a path's latency to arrive).
+__device__ uint32_t host_sample(const Glob& g, int32_t h, uint64_t t) {
+    const shd_tcp_hostrec* r = &g.hrec[h];
+    if (!r->t_first || r->t_last < t - g.hser_ival) return 0;
+    const uint32_t at = atomicAdd(g.nhser, 1u);
+    if (at >= g.hser_cap) return SHD_TCP_ERR_HSERIES;
+    shd_host_sample* d = &g.hser[at];
+    d->t = t;
+    d->rec = *r;
+    d->rec.host = g.h0 + h;
+    d->rec.depth_end = (uint32_t)(r->router_enqueued - r->router_dequeued - r->router_dropped);
+    d->rec._pad = 0;
+    return 0;
 }
-// the lane's next event, at time t, lies at or past the host's boundary (and
-// in the window): the touched records are sampled with that boundary's label,
-// and the next boundary is the first one after t -- an event at a boundary
-// opens the interval after it.  Returns the lane's new limit.
+// how far host h's lane runs before it has to look at a boundary: the
+// window's end, or its next boundary of either series when that comes first
+__device__ __noinline__ uint64_t series_limit(const Glob& g, int32_t h, uint64_t wend) {
+    uint64_t lim = wend;
+    if (g.ser_on & 1u) {
+        const uint64_t nb = g.ser_next[h];
+        lim = nb < lim ? nb : lim;
+    }
+    if (g.ser_on & 2u) {
+        const uint64_t nb = g.hser_next[h];
+        lim = nb < lim ? nb : lim;
+    }
+    return lim;
+}
+// the lane's next event, at time t, lies at or past a boundary of the host
+// (and in the window): for each series whose boundary it is, the touched
+// records are sampled with that boundary's label, and the next boundary is
+// the first one after t -- an event at a boundary opens the interval after
+// it.  Returns the lane's new limit.
 __device__ __noinline__ uint64_t series_cross(L& c, uint64_t t, uint64_t wend) {
     const Glob& g = *c.g;
-    c.H->err |= series_take(g, c.h, g.ser_next[c.h]);
-    const uint64_t nb = (t / g.ser_ival + 1) * g.ser_ival;
-    g.ser_next[c.h] = nb;
-    return nb < wend ? nb : wend;
+    uint64_t lim = wend;
+    if (g.ser_on & 1u) {
+        uint64_t nb = g.ser_next[c.h];
+        if (t >= nb) {
+            c.H->err |= series_take(g, c.h, nb);
+            nb = (t / g.ser_ival + 1) * g.ser_ival;
+            g.ser_next[c.h] = nb;
+        }
+        lim = nb < lim ? nb : lim;
+    }
+    if (g.ser_on & 2u) {
+        uint64_t nb = g.hser_next[c.h];
+        if (t >= nb) {
+            c.H->err |= host_sample(g, c.h, nb);
+            nb = (t / g.hser_ival + 1) * g.hser_ival;
+            g.hser_next[c.h] = nb;
+        }
+        lim = nb < lim ? nb : lim;
+    }
+    return lim;
 }
 // the end of the run: what is still touched, when its boundary lies before
 // the end (one thread per host; the flow record itself is the end state)
@@ -3364,6 +3432,17 @@ __global__ void k_tcp_series_flush(Glob g) {
     const uint64_t nb = g.ser_next[h];
     if (nb >= g.end_time) return;
     const uint32_t err = series_take(g, h, nb);
+    if (err) g.host[h].err |= err;
+}
+// the same for the host records' series: the record as the run left it is its
+// host's sample at the boundary its last touches belong to, when that lies
+// before the end
+__global__ void k_tcp_hseries_flush(Glob g) {
+    const int32_t h = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (h >= g.nloc) return;
+    const uint64_t nb = g.hser_next[h];
+    if (nb >= g.end_time) return;
+    const uint32_t err = host_sample(g, h, nb);
     if (err) g.host[h].err |= err;
 }
 __global__ void k_tcp_series_init(uint64_t* __restrict__ next, int32_t n, uint64_t ival) {
@@ -3420,8 +3499,9 @@ __global__ void __launch_bounds__(64) k_tcp_round(Glob g) {
         if (!ingest_mail(c, s)) break;
     TCP_PROF(0);
     uint64_t nev = 0;
-    // The flow time series costs the event loop nothing per event: the lane
-    // runs its events up to `lim`, the window's end or, with the series, its
+    // The two series (the flow records', the host records') cost the event
+    // loop nothing per event: the lane
+    // runs its events up to `lim`, the window's end or, with a series, its
     // host's next boundary when that comes first; there the touched records
     // are sampled and the loop goes on to the next limit (series_cross).
     // Without the option lim is wend and the outer loop runs once: one test of
@@ -3754,7 +3834,7 @@ enum WsSlot {
     kWsAppSpec, kWsAppPeer, kWsDestCum, kWsHostClass, kWsIpAll, kWsBwu, kWsBwd, kWsProcPort, kWsPortNew, kWsXsend,
     kWsXrecv, kWsPmine, kWsPall, kWsXcnt, kWsGmine, kWsGall, kWsPcap, kWsNpcap, kWsPcapSlot, kWsHostHb, kWsSockOff, kWsDir, kWsIfq,
     kWsProcOff, kWsFlow, kWsFlowCnt, kWsFlowOff, kWsFlowOut, kWsPacc, kWsPtab, kWsPtFull, kWsPtCnt, kWsPtOff,
-    kWsPtOut, kWsSer, kWsNser, kWsSerNext, kWsSerMap, kWsHrec, kWsSlots
+    kWsPtOut, kWsSer, kWsNser, kWsSerNext, kWsSerMap, kWsHrec, kWsHser, kWsNhser, kWsHserNext, kWsSlots
 };
 // what the library allocates for a result: the public struct first (its size
 // is pinned), then the flow records shd_tcp_result_flows and the path records
@@ -3770,6 +3850,9 @@ struct TcpResultX {
     shd_tcp_series_info series_info;
     shd_tcp_hostrec* hosts;   // shd_tcp_result_hosts: n_local_hosts records, or null without the option
     uint64_t n_hosts;
+    shd_host_sample* hseries;   // shd_tcp_result_host_series: sorted by (host, t)
+    uint64_t n_hseries;
+    shd_tcp_series_info hseries_info;
 };
 // The pair table's capacity (shdtcp.h): a power of two at least twice the
 // most ordered vertex pairs the model's hosts can send over -- min(Vu^2, E + 2
@@ -3911,19 +3994,37 @@ static hipError_t pcap_drain(TcpPcap& pc, const Glob& g, hipStream_t st) {
 constexpr uint32_t kSeriesCapMin = 1u << 20;   // the sample array's default capacity: this, or kSeriesPerSlot
 constexpr uint32_t kSeriesPerSlot = 4;         // records per socket slot when that is more
 constexpr uint32_t kSeriesCapMax = 1u << 26;
-struct TcpSeries {
-    std::vector<shd_tcp_sample> recs;
+template <class Rec>
+struct TcpSamples {
+    std::vector<Rec> recs;
     uint32_t cnt = 0;   // the append counter as last copied
     uint64_t drains = 0, rounds_since = 0;
     uint32_t peak = 0;
     double drain_ms = 0;   // host wall time of the drains (SHD_TCP_SERIES_TIMING prints it)
+    bool full = false;     // a drain found the counter past the capacity (the host records' series stops there)
 };
+using TcpSeries = TcpSamples<shd_tcp_sample>;
+// the host records' series (SHD_TCP_OPT_HOST_SERIES) is kept the same way
+constexpr uint32_t kHseriesCapMin = 1u << 18;   // the sample array's default capacity: this, or kHseriesPerHost
+constexpr uint32_t kHseriesPerHost = 16;        // records per local host when that is more
+constexpr uint32_t kHseriesCapMax = 1u << 24;
+using TcpHostSeries = TcpSamples<shd_host_sample>;
 // the array's used part (sr.cnt: the counter just copied; past the capacity
 // nothing was written) to host memory and the counter back to zero, on the
 // run's stream: the array never carries samples from one drain to the next
-static hipError_t series_drain(TcpSeries& sr, const Glob& g, hipStream_t st) {
+// (arr [cap] and *cnt: Glob's ser / nser, or hser / nhser).  The two series
+// differ in what a full array means.  The flow series goes on: the counter is
+// reset, later samples are taken, and the error bit says that some are
+// missing (sr.full is then only the last drain's finding; nothing reads it).
+// The host records' series ends there (stop_full, hseries_drain_due says why):
+// a counter past the capacity stays where it is, so that every later append
+// fails as well, and sr.full keeps later drains away.
+template <class Rec>
+static hipError_t series_drain(TcpSamples<Rec>& sr, const Rec* arr, uint32_t* cnt, uint32_t cap, hipStream_t st,
+                               bool stop_full = false) {
     sr.rounds_since = 0;
-    const uint32_t n = std::min(sr.cnt, g.ser_cap);
+    const uint32_t n = std::min(sr.cnt, cap);
+    sr.full = sr.cnt > cap;
     if (!sr.cnt) return hipSuccess;
     const auto t0 = std::chrono::steady_clock::now();
     sr.cnt = 0;
@@ -3932,10 +4033,10 @@ static hipError_t series_drain(TcpSeries& sr, const Glob& g, hipStream_t st) {
         sr.peak = std::max(sr.peak, n);
         const size_t at = sr.recs.size();
         sr.recs.resize(at + n);
-        const hipError_t e = hipMemcpyAsync(sr.recs.data() + at, g.ser, sizeof(shd_tcp_sample) * n, hipMemcpyDeviceToHost, st);
+        const hipError_t e = hipMemcpyAsync(sr.recs.data() + at, arr, sizeof(Rec) * n, hipMemcpyDeviceToHost, st);
         if (e != hipSuccess) return e;
     }
-    hipError_t e = hipMemsetAsync(g.nser, 0, sizeof(uint32_t), st);
+    hipError_t e = (stop_full && sr.full) ? hipSuccess : hipMemsetAsync(cnt, 0, sizeof(uint32_t), st);
     if (e != hipSuccess) return e;
     e = hipStreamSynchronize(st);
     sr.drain_ms += ms_since(t0);
@@ -4086,6 +4187,13 @@ static int tcp_plan(const shd_tcp_model* m, int32_t world, int32_t me, TcpPlan& 
     if ((m->options & SHD_TCP_OPT_SERIES) &&
         (!(m->options & SHD_TCP_OPT_FLOWS) || !m->series_interval_us || m->series_cap > (int32_t)kSeriesCapMax))
         return -22;
+    // the host records' series samples host records at an interval: the same, and
+    // a boundary's index fits 32 bits (the packet engine's limit, shdgpu.h)
+    if ((m->options & SHD_TCP_OPT_HOST_SERIES) &&
+        (!(m->options & SHD_TCP_OPT_HOSTS) || !m->host_series_interval_us ||
+         m->host_series_cap > (int32_t)kHseriesCapMax ||
+         m->end_time / (1000ull * m->host_series_interval_us) >= (1ull << 32)))
+        return -22;
     // path_cache mode: a built cache of an undirected graph (the directed
     // lookup reruns rows, topology.c:1987-1990: not restated on the device)
     if (pc && (!pc->built || pc->directed || (!pc->complete && !pc->d_row))) return -22;
@@ -4174,6 +4282,7 @@ struct TcpLive {
     TCtl hctl;
     TcpPcap pcp;
     TcpSeries ser;
+    TcpHostSeries hser;
 };
 
 // One run's hold on the device: the workspace (locked for the run), the
@@ -4436,7 +4545,7 @@ static int setup_options(TcpRun& r, const shd_tcp_model* m, const TcpPlan& p) {
         HCHECK(hipMemset(g.nser, 0, sizeof(uint32_t)));
         k_tcp_series_init<<<(unsigned)((nloc + 255) / 256), 256>>>(g.ser_next, p.nloc, g.ser_ival);
         HCHECK(hipGetLastError());
-        g.ser_on = 1;
+        g.ser_on |= 1u;
     }
     if (m->options & SHD_TCP_OPT_PATHS) {   // an accumulator beside every slot, the pair table, and the gather's flags and offsets
         const uint32_t cap = r.paths.cap = tcp_path_slots(m, p.hvi);
@@ -4455,6 +4564,21 @@ static int setup_options(TcpRun& r, const shd_tcp_model* m, const TcpPlan& p) {
         WS_NEED(r.alloc(kWsHrec, &g.hrec, nloc), "shd_tcp_run: no device memory for the host records of %d hosts\n", p.nloc);
         HCHECK(hipMemset(g.hrec, 0, sizeof(shd_tcp_hostrec) * nloc));
         g.stat_on |= 8u;
+    }
+    if (m->options & SHD_TCP_OPT_HOST_SERIES) {   // the engine's sample array and its counter, a boundary per host
+        g.hser_cap = m->host_series_cap > 0
+                         ? (uint32_t)m->host_series_cap
+                         : (uint32_t)std::min<uint64_t>(std::max<uint64_t>(kHseriesCapMin, kHseriesPerHost * (uint64_t)nloc),
+                                                        kHseriesCapMax);
+        WS_NEED(r.alloc(kWsHser, &g.hser, (size_t)g.hser_cap) && r.alloc(kWsNhser, &g.nhser, 1) &&
+                    r.alloc(kWsHserNext, &g.hser_next, nloc),
+                "shd_tcp_run: no device memory for the host records' series (%u samples, %.1f GB); "
+                "set a smaller host_series_cap\n", g.hser_cap, sizeof(shd_host_sample) * (double)g.hser_cap / 1e9);
+        HCHECK(hipMemset(g.nhser, 0, sizeof(uint32_t)));
+        g.hser_ival = 1000ull * m->host_series_interval_us;
+        k_tcp_series_init<<<(unsigned)((nloc + 255) / 256), 256>>>(g.hser_next, p.nloc, g.hser_ival);
+        HCHECK(hipGetLastError());
+        g.ser_on |= 2u;
     }
     return 0;
 }
@@ -4585,8 +4709,13 @@ static int pcap_counts_back(const TcpRun& r, TcpPcap& pcp) {
     return 0;
 }
 static int series_count_back(const TcpRun& r, TcpSeries& ser) {
-    if (!r.g.ser_on) return 0;
+    if (!r.g.ser) return 0;
     HCHECK(hipMemcpyAsync(&ser.cnt, r.g.nser, sizeof(uint32_t), hipMemcpyDeviceToHost, r.st));
+    return 0;
+}
+static int hseries_count_back(const TcpRun& r, TcpHostSeries& hs) {
+    if (!r.g.hser) return 0;
+    HCHECK(hipMemcpyAsync(&hs.cnt, r.g.nhser, sizeof(uint32_t), hipMemcpyDeviceToHost, r.st));
     return 0;
 }
 // the drain of the counts just copied, if it is due: always (`now`: a batch's
@@ -4600,8 +4729,20 @@ static int pcap_drain_due(const TcpRun& r, TcpPcap& pcp, bool now) {
     return 0;
 }
 static int series_drain_due(const TcpRun& r, TcpSeries& ser, bool now) {
-    if (!r.g.ser_on) return 0;
-    if (now || ++ser.rounds_since >= 64 || ser.cnt > r.g.ser_cap / 2) HCHECK(series_drain(ser, r.g, r.st));
+    if (!r.g.ser) return 0;
+    if (now || ++ser.rounds_since >= 64 || ser.cnt > r.g.ser_cap / 2)
+        HCHECK(series_drain(ser, r.g.ser, r.g.nser, r.g.ser_cap, r.st));
+    return 0;
+}
+// A host whose append found the array full stops (its error bit), and the
+// hosts it talks to run on without it: a sample taken after that is no sample
+// of the model's run.  So the first drain that finds the counter past the
+// capacity is the last one -- what the array holds was appended before any
+// host stopped -- and the counter stays there, which fails every later append.
+static int hseries_drain_due(const TcpRun& r, TcpHostSeries& hs, bool now) {
+    if (!r.g.hser || hs.full) return 0;
+    if (now || ++hs.rounds_since >= 64 || hs.cnt > r.g.hser_cap / 2)
+        HCHECK(series_drain(hs, r.g.hser, r.g.nhser, r.g.hser_cap, r.st, true));
     return 0;
 }
 // the control word and the counters after a batch or a round, then the drains
@@ -4609,9 +4750,11 @@ static int round_end(const TcpRun& r, TcpLive& lv, bool drain_now) {
     HCHECK(hipMemcpyAsync(&lv.hctl, r.g.ctl, sizeof(TCtl), hipMemcpyDeviceToHost, r.st));
     TRY(pcap_counts_back(r, lv.pcp));
     TRY(series_count_back(r, lv.ser));
+    TRY(hseries_count_back(r, lv.hser));
     HCHECK(hipStreamSynchronize(r.st));
     TRY(pcap_drain_due(r, lv.pcp, drain_now));
-    return series_drain_due(r, lv.ser, drain_now);
+    TRY(series_drain_due(r, lv.ser, drain_now));
+    return hseries_drain_due(r, lv.hser, drain_now);
 }
 
 // One engine: rounds run in batches of kBatch (window kernel, round kernel)
@@ -4774,12 +4917,19 @@ static int tcp_rounds(TcpRun& r, shd_comm* comm, shd_tcp_result* res) {
     TRY(pcap_counts_back(r, lv.pcp));
     if (g.pcap_on) HCHECK(hipStreamSynchronize(r.st));
     TRY(pcap_drain_due(r, lv.pcp, true));
-    if (g.ser_on) {   // the records still touched (k_tcp_series_flush), with what the array holds since the last drain
+    if (g.ser) {   // the records still touched (k_tcp_series_flush), with what the array holds since the last drain
         k_tcp_series_flush<<<(unsigned)((g.nloc + 255) / 256), 256, 0, r.st>>>(g);
         HCHECK(hipGetLastError());
         TRY(series_count_back(r, lv.ser));
         HCHECK(hipStreamSynchronize(r.st));
         TRY(series_drain_due(r, lv.ser, true));
+    }
+    if (g.hser) {   // the records touched since their host's last boundary (k_tcp_hseries_flush), likewise
+        if (!lv.hser.full) k_tcp_hseries_flush<<<(unsigned)((g.nloc + 255) / 256), 256, 0, r.st>>>(g);
+        HCHECK(hipGetLastError());
+        TRY(hseries_count_back(r, lv.hser));
+        HCHECK(hipStreamSynchronize(r.st));
+        TRY(hseries_drain_due(r, lv.hser, true));
     }
     HCHECK(hipEventRecord(r.e1, r.st));
     HCHECK(hipEventSynchronize(r.e1));
@@ -4874,7 +5024,7 @@ static int collect_flows(const TcpRun& r, TcpSeries& ser, int32_t ns, TcpResultX
         HCHECK(hipEventElapsedTime(&fms, r.e0, r.e1));
         fprintf(stderr, "shd_tcp_run: %u flow records of %d slots gathered in %.3f ms\n", nf, ns, fms);
     }
-    return g.ser_on ? collect_series(r, ser, ns, nf, resx) : 0;
+    return g.ser ? collect_series(r, ser, ns, nf, resx) : 0;
 }
 
 // the path records: the accumulators folded, the table compacted (k_tcp_path_*), the records named and sorted
@@ -5034,12 +5184,31 @@ static int collect_host_scalars(const std::vector<DHost>& hout, shd_tcp_result* 
     return 0;
 }
 
+// the host records' series: the drained samples sorted by (host, t)
+static int collect_host_series(const Glob& g, TcpHostSeries& hs, TcpResultX* resx) {
+    const size_t n = hs.recs.size();
+    resx->hseries_info.drains = hs.drains;
+    resx->hseries_info.peak = hs.peak;
+    resx->hseries_info.capacity = g.hser_cap;
+    TRY(res_alloc(&resx->hseries, n));
+    std::sort(hs.recs.begin(), hs.recs.end(), [](const shd_host_sample& a, const shd_host_sample& b) {
+        return a.rec.host != b.rec.host ? a.rec.host < b.rec.host : a.t < b.t;
+    });
+    if (n) memcpy(resx->hseries, hs.recs.data(), sizeof(shd_host_sample) * n);
+    resx->n_hseries = n;
+    if (getenv("SHD_TCP_SERIES_TIMING"))   // the drains' host wall time (copies and their waits), for measurements
+        fprintf(stderr, "shd_tcp_run: %zu host samples in %llu drains (peak %u of %u), drains %.3f ms\n", n,
+                (unsigned long long)hs.drains, hs.peak, g.hser_cap, hs.drain_ms);
+    return 0;
+}
+
 // the local hosts' records in one copy; the host names them and reads the queue's last length
-static int collect_host_records(const Glob& g, const std::vector<DHost>& hout, TcpResultX* resx) {
+static int collect_host_records(const Glob& g, const std::vector<DHost>& hout, TcpHostSeries& hs, TcpResultX* resx) {
     const auto t0 = std::chrono::steady_clock::now();
     const int32_t nloc = g.nloc;
     TRY(res_alloc(&resx->hosts, (size_t)nloc));
     HCHECK(hipMemcpy(resx->hosts, g.hrec, sizeof(shd_tcp_hostrec) * (size_t)nloc, hipMemcpyDeviceToHost));
+    if (g.hser) TRY(collect_host_series(g, hs, resx));
     for (int32_t i = 0; i < nloc; i++) {
         resx->hosts[i].host = g.h0 + i;
         resx->hosts[i].depth_end = hout[i].cq_n;
@@ -5131,7 +5300,7 @@ static int tcp_collect(TcpRun& run, const shd_tcp_model* m, const TcpPlan& p, sh
     if (p.any_pcap) TRY(collect_pcap(r.live.pcp, g.nloc, res));
     TRY(collect_control(g, pc, p.V, sch, res));
     TRY(collect_host_scalars(hout, res));
-    if (g.hrec) TRY(collect_host_records(g, hout, resx));
+    if (g.hrec) TRY(collect_host_records(g, hout, run.live.hser, resx));
     if (g.path_on && pc && !res->error) collect_path_packets(pc, resx);
     if (g.node) TRY(collect_node_counters(g, hout, res));
     if (g.trace) TRY(collect_lines(g, hout, res));
@@ -5222,6 +5391,7 @@ extern "C" void shd_tcp_result_free(shd_tcp_result* r) {
     free(((TcpResultX*)r)->paths);
     free(((TcpResultX*)r)->series);
     free(((TcpResultX*)r)->hosts);
+    free(((TcpResultX*)r)->hseries);
     free(r);
 }
 
@@ -5230,6 +5400,16 @@ extern "C" int shd_tcp_result_hosts(const shd_tcp_result* r, const shd_tcp_hostr
     const TcpResultX* x = (const TcpResultX*)r;
     *recs = x->n_hosts ? x->hosts : nullptr;
     *n = x->n_hosts;
+    return 0;
+}
+
+extern "C" int shd_tcp_result_host_series(const shd_tcp_result* r, const shd_host_sample** recs, uint64_t* n,
+                                          shd_tcp_series_info* info) {
+    if (!r || !recs || !n) return -22;
+    const TcpResultX* x = (const TcpResultX*)r;
+    *recs = x->n_hseries ? x->hseries : nullptr;   // (a run with the option and no sample: NULL and 0 as well)
+    *n = x->n_hseries;
+    if (info) *info = x->hseries_info;
     return 0;
 }
 

@@ -204,13 +204,13 @@ class TcpModel(C.Structure):
     _fields_ = [("n_hosts", C.c_int32), ("n_procs", C.c_int32),
                 ("host_ip", P(C.c_uint32)), ("host_seed", P(C.c_uint32)),
                 ("bw_down_kibps", P(C.c_uint64)), ("bw_up_kibps", P(C.c_uint64)),
-                ("n_vertices", C.c_int32), ("host_vertex", P(C.c_int32)),
+                ("n_vertices", C.c_int32), ("host_series_cap", C.c_int32), ("host_vertex", P(C.c_int32)),
                 ("path_lat_ms", P(C.c_double)), ("path_rel", P(C.c_double)),
                 ("proc_host", P(C.c_int32)), ("proc_start", P(C.c_uint64)), ("proc_peer", P(C.c_int32)),
                 ("end_time", C.c_uint64), ("heartbeat_interval", C.c_uint64),
                 ("tcp_bytes", C.c_uint32), ("recv_buf", C.c_uint32), ("send_buf", C.c_uint32),
                 ("tcp_window", C.c_uint32), ("packets_per_host", C.c_uint32), ("qdisc", C.c_uint32),
-                ("options", C.c_uint32), ("path_cache", C.c_void_p),
+                ("options", C.c_uint32), ("host_series_interval_us", C.c_uint32), ("path_cache", C.c_void_p),
                 ("proc_app", P(C.c_int32)), ("app_spec", P(C.c_uint32)), ("n_app_specs", C.c_int32),
                 ("udp_payload", C.c_uint32), ("app_peer", P(C.c_int32)), ("dest_cum", P(C.c_double)),
                 ("host_class", P(C.c_uint8)), ("n_classes", C.c_int32), ("series_cap", C.c_int32),
@@ -341,6 +341,13 @@ TCP_OPT_HOSTS = 8   # SHD_TCP_OPT_HOSTS (shd_tcp_model.options): a record per ho
 TCP_HOSTREC_DTYPE = np.dtype([(n, "<i4" if t is C.c_int32 else "<u4" if t is C.c_uint32 else "<u8")
                               if n != "sojourn_hist" else (n, "<u4", (16,)) for n, t in TcpHostRec._fields_])
 assert TCP_HOSTREC_DTYPE.itemsize == C.sizeof(TcpHostRec) == 232
+TCP_OPT_HOST_SERIES = 16   # SHD_TCP_OPT_HOST_SERIES (with TCP_OPT_HOSTS): per-interval samples of the host records
+TCP_ERR_HSERIES = 8192     # SHD_TCP_ERR_HSERIES: the host records' sample array filled between two drains
+
+
+class HostSample(C.Structure):
+    """shd_host_sample (include/shdtcp.h): one host's record at a boundary"""
+    _fields_ = [("t", C.c_uint64), ("rec", TcpHostRec)]
 
 
 TCP_QUERY_DTYPE = np.dtype([("time", "<u8"), ("seq", "<u8"), ("host", "<u4"), ("src", "<u4"), ("index", "<u4"),
@@ -362,6 +369,7 @@ _SIGS = {
     "shd_tcp_result_paths": (C.c_int, [P(TcpResult), P(P(TcpPath)), P(C.c_uint64)]),
     "shd_tcp_result_series": (C.c_int, [P(TcpResult), P(P(TcpSample)), P(C.c_uint64), P(TcpSeriesInfo)]),
     "shd_tcp_result_hosts": (C.c_int, [P(TcpResult), P(P(TcpHostRec)), P(C.c_uint64)]),
+    "shd_tcp_result_host_series": (C.c_int, [P(TcpResult), P(P(HostSample)), P(C.c_uint64), P(TcpSeriesInfo)]),
     "shd_tcp_keep_workspace": (None, [C.c_int32]),
     "shd_pcap_format": (C.c_size_t, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int32, C.c_void_p, C.c_size_t]),
     "shd_pcap_write_host": (C.c_int, [C.c_char_p, C.c_char_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32]),
@@ -711,12 +719,27 @@ def merge_tcp_hosts(parts) -> np.ndarray:
 
 # one sample of a host-record series (struct shd_host_sample, include/shdtcp.h): the boundary and the record
 HOST_SAMPLE_DTYPE = np.dtype([("t", "<u8"), ("rec", TCP_HOSTREC_DTYPE)])
+assert HOST_SAMPLE_DTYPE.itemsize == C.sizeof(HostSample) == 240
 HOST_SERIES_CSV_FIELDS = ("t",) + HOSTS_CSV_FIELDS
+
+
+def tcp_result_host_series(res):
+    """The host records' series of a shd_tcp_result (pointer) as a
+    HOST_SAMPLE_DTYPE array of its own, sorted by (host, t)
+    (shd_tcp_result_host_series), and the drains' figures dict(drains, peak,
+    capacity); empty and zeros when the model did not set TCP_OPT_HOST_SERIES."""
+    recs, n, info = P(HostSample)(), C.c_uint64(), TcpSeriesInfo()
+    check(lib().shd_tcp_result_host_series(res, C.byref(recs), C.byref(n), C.byref(info)),
+          "shd_tcp_result_host_series")
+    d = dict(drains=int(info.drains), peak=int(info.peak), capacity=int(info.capacity))
+    if not n.value:
+        return np.zeros(0, dtype=HOST_SAMPLE_DTYPE), d
+    return np.frombuffer(C.string_at(recs, n.value * HOST_SAMPLE_DTYPE.itemsize), dtype=HOST_SAMPLE_DTYPE).copy(), d
 
 
 def write_host_series_csv(path, samples) -> int:
     """Write host-record samples (HOST_SAMPLE_DTYPE, as sim.Engine.host_series()
-    returns them) as CSV: a header line (HOST_SERIES_CSV_FIELDS: t, then
+    and tcp.run(..., hosts=True, host_series_us=N) return them) as CSV: a header line (HOST_SERIES_CSV_FIELDS: t, then
     write_hosts_csv's columns), then one line per sample in the samples'
     order; times in ns.  Returns the number of rows."""
     a = np.asarray(samples, dtype=HOST_SAMPLE_DTYPE)

@@ -101,7 +101,7 @@ def serial_first_queries(queries: np.ndarray):
 def run(model: S.ModelArrays, g: S.GraphArrays, ips, procs, peers, nbytes=20000, trace=True,
         recv_buf=RECV_BUF, send_buf=SEND_BUF, tcp_window=TCP_WINDOW, packets_per_host=0, guess_reversed=False,
         node=False, qdisc=0, mode="device", udp=None, comm=None, pcap=None, flows=False, paths=False,
-        series_us=0, series_cap=0, hosts=False):
+        series_us=0, series_cap=0, hosts=False, host_series_us=0, host_series_cap=0):
     """Run the TCP echo model on the GPU: procs = [(host, start ns)], peers =
     [-1 | server process]; ips: host-order uint32 per host.  Returns
     dict(lines=[(t, h, line)] in each host's order, next_event_id,
@@ -160,6 +160,15 @@ def run(model: S.ModelArrays, g: S.GraphArrays, ips, procs, peers, nbytes=20000,
     in host order, record i for host first_host + i.  With comm the array is
     this rank's own hosts'; S.merge_tcp_hosts joins the ranks',
     S.write_hosts_csv writes them.
+    host_series_us: with hosts, the host records' series
+    (shd_tcp_model.options & SHD_TCP_OPT_HOST_SERIES) at that interval in
+    microseconds: the result then has host_series, a S.HOST_SAMPLE_DTYPE array
+    sorted by (host, t) -- a host's whole record for every interval in which
+    one of its statuses was raised, labelled with the interval's end -- and
+    host_series_info dict(drains, peak, capacity); host_series_cap: records of
+    the device's sample array (0: the default).  With comm the samples are this
+    rank's own hosts'; S.merge_host_series joins the ranks', S.host_progress
+    makes a host's dense curve, S.write_host_series_csv writes the samples.
     The model's bootstrap period (model.struct.bootstrap_end) and per-host
     heartbeat intervals (model.host_heartbeat) run as the reference's loop runs
     them (shd_tcp_model.bootstrap_end / host_heartbeat), on one engine and
@@ -176,7 +185,7 @@ def run(model: S.ModelArrays, g: S.GraphArrays, ips, procs, peers, nbytes=20000,
             out = _run_once(model, ips, procs, peers, None, None, hv.astype(np.int32), nbytes, trace, recv_buf,
                             send_buf, tcp_window, packets_per_host, node, qdisc, pc=pc, udp=udp, comm=comm,
                             pcap=pcap, flows=flows, paths=paths, series_us=series_us, series_cap=series_cap,
-                            hosts=hosts)
+                            hosts=hosts, host_series_us=host_series_us, host_series_cap=host_series_cap)
         finally:
             pc.close()
         if out is not None:
@@ -189,7 +198,8 @@ def run(model: S.ModelArrays, g: S.GraphArrays, ips, procs, peers, nbytes=20000,
     for runs in range(1, 9):
         out = _run_once(model, ips, procs, peers, lat, rel, hvi, nbytes, trace, recv_buf, send_buf, tcp_window,
                         packets_per_host, node, qdisc, udp=udp, comm=comm, pcap=pcap, flows=flows, paths=paths,
-                        series_us=series_us, series_cap=series_cap, hosts=hosts)
+                        series_us=series_us, series_cap=series_cap, hosts=hosts, host_series_us=host_series_us,
+                        host_series_cap=host_series_cap)
         if paths:   # the table's indices back to graph vertices
             p = out["paths"]
             names = np.asarray(att, dtype=np.int32)
@@ -215,7 +225,7 @@ def run(model: S.ModelArrays, g: S.GraphArrays, ips, procs, peers, nbytes=20000,
 
 def fill_model(model, ips, procs, peers, lat, rel, hvi, nbytes, recv_buf=RECV_BUF, send_buf=SEND_BUF,
                tcp_window=TCP_WINDOW, packets_per_host=0, qdisc=0, pc=None, udp=None, pcap=None, flows=False,
-               paths=False, series_us=0, series_cap=0, hosts=False):
+               paths=False, series_us=0, series_cap=0, hosts=False, host_series_us=0, host_series_cap=0):
     """The shd_tcp_model of one run (no device needed): (TcpModel, the arrays
     its pointers refer to -- keep them alive as long as the struct is used).
     The model's bootstrap period and per-host heartbeat intervals
@@ -224,7 +234,9 @@ def fill_model(model, ips, procs, peers, lat, rel, hvi, nbytes, recv_buf=RECV_BU
     the model's options; paths: SHD_TCP_OPT_PATHS; series_us: SHD_TCP_OPT_SERIES
     at that interval (the caller sets flows with it: the library refuses the
     bit alone), series_cap: the sample array's records (0: the default); hosts:
-    SHD_TCP_OPT_HOSTS."""
+    SHD_TCP_OPT_HOSTS; host_series_us: SHD_TCP_OPT_HOST_SERIES at that interval
+    (the library refuses it without hosts), host_series_cap: its sample array's
+    records (0: the default)."""
     m = model.struct
     H = int(m.n_hosts)
     keep = dict(ip=np.ascontiguousarray(ips, dtype=np.uint32), hv=np.ascontiguousarray(hvi, dtype=np.int32),
@@ -260,7 +272,10 @@ def fill_model(model, ips, procs, peers, lat, rel, hvi, nbytes, recv_buf=RECV_BU
     tm.packets_per_host = packets_per_host
     tm.qdisc = int(qdisc)   # --interface-qdisc: 0 fifo, 1 rr
     tm.options = (S.TCP_OPT_FLOWS if flows else 0) | (S.TCP_OPT_PATHS if paths else 0) | \
-        (S.TCP_OPT_SERIES if series_us else 0) | (S.TCP_OPT_HOSTS if hosts else 0)
+        (S.TCP_OPT_SERIES if series_us else 0) | (S.TCP_OPT_HOSTS if hosts else 0) | \
+        (S.TCP_OPT_HOST_SERIES if host_series_us else 0)
+    tm.host_series_interval_us = int(host_series_us)
+    tm.host_series_cap = int(host_series_cap)
     tm.series_interval_us = int(series_us)
     tm.series_cap = int(series_cap)
     if pc is not None:
@@ -287,13 +302,14 @@ def fill_model(model, ips, procs, peers, lat, rel, hvi, nbytes, recv_buf=RECV_BU
 
 def _run_once(model, ips, procs, peers, lat, rel, hvi, nbytes, trace, recv_buf, send_buf, tcp_window,
               packets_per_host, node=False, qdisc=0, pc=None, udp=None, comm=None, pcap=None, flows=False,
-              paths=False, series_us=0, series_cap=0, hosts=False):
+              paths=False, series_us=0, series_cap=0, hosts=False, host_series_us=0, host_series_cap=0):
     """one shd_tcp_run on the given path tables, or with pc (sim.PathCache) on
     the cache itself (hvi: graph vertices then); None when that run's
     first-touch choices were contradicted (SHD_TCP_ERR_FIRST_TOUCH)"""
     tm, keep = fill_model(model, ips, procs, peers, lat, rel, hvi, nbytes, recv_buf, send_buf, tcp_window,
                           packets_per_host, qdisc, pc=pc, udp=udp, pcap=pcap, flows=flows, paths=paths,
-                          series_us=series_us, series_cap=series_cap, hosts=hosts)
+                          series_us=series_us, series_cap=series_cap, hosts=hosts, host_series_us=host_series_us,
+                          host_series_cap=host_series_cap)
     res = C.POINTER(S.TcpResult)()
     bits = (S.TCP_TRACE_STATUS if trace else 0) | (S.TCP_TRACE_NODE if node else 0)
     if comm is not None:
@@ -334,6 +350,8 @@ def _run_once(model, ips, procs, peers, lat, rel, hvi, nbytes, trace, recv_buf, 
             out["paths"] = S.tcp_result_paths(res)
         if hosts:
             out["hosts"] = S.tcp_result_hosts(res)
+        if host_series_us:
+            out["host_series"], out["host_series_info"] = S.tcp_result_host_series(res)
         if pcap is not None:
             off = np.ctypeslib.as_array(r.pcap_off, shape=(HL + 1,)).copy()
             recs = np.frombuffer(C.string_at(r.pcap_records, int(off[-1]) * S.PCAP_DTYPE.itemsize),
